@@ -22,8 +22,20 @@ fake cluster + HTTP server), one process per GPU; ranks synchronise per
 step via torch.distributed (RCCL on GPU, gloo on CPU). `value` is the
 whole-job aggregate pods/sec over all ranks, timed as MAX over ranks.
 
+A plain run does only what the headline figure needs: set up, warm up,
+time the steps, print the result line. Everything else the benchmark can
+measure (today: the measured xGMI hop/bandwidth matrix on a multi-GPU box,
+which runs in a subprocess of its own) sits behind --full.
+
+Inputs are deterministic: pod names, uids and tie-breaks derive from
+(rank, step, index) alone, so two runs with the same arguments schedule
+identical pods. --dump-outputs DIR writes what the last timed step
+computed (per pod: feasible nodes, node scores, bound node, allocated
+cards) as DIR/<name>.npy for output-for-output comparison of two builds.
+
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
         [--policy binpack|spread|random] [--no-http] [--no-verify]
+        [--dump-outputs DIR] [--full]
 For N>1 the driver launches this under torch.distributed.run.
 """
 from __future__ import annotations
@@ -36,8 +48,16 @@ import statistics
 import threading
 import time
 import uuid
+import zlib
 
 GiB = 1024**3
+
+
+def _tiebreak(uid: str) -> int:
+    """Stable (process-independent) hash of a pod uid: builtin hash() of a
+    str is salted per process, which would make placements differ from run
+    to run."""
+    return zlib.crc32(uid.encode())
 
 
 # ---------------------------------------------------------------- workload
@@ -60,7 +80,7 @@ def mixed_pod_spec(i: int, step: int, rank: int, pad_bytes: int = 0):
         req["elasticgpu.io/gpu-memory"] = str(mem)
     pod = {
         "metadata": {"name": name, "namespace": "default",
-                     "uid": str(uuid.uuid4())},
+                     "uid": str(uuid.uuid5(uuid.NAMESPACE_OID, name))},
         "spec": {"containers": [{"name": "main",
                                  "resources": {"requests": req,
                                                "limits": dict(req)}}]},
@@ -213,6 +233,8 @@ class BenchPipeline:
         self.latencies: list[float] = []
         self._lat_mu = threading.Lock()
         self.bind_retries = 0
+        self._capture = None  # --dump-outputs: arrays of the last step
+        self._capture_row = {}
         self.port = None
         self._server = None
         self._server_thread = None
@@ -289,11 +311,14 @@ class BenchPipeline:
 
     # -- one step --
 
-    def step(self, step_idx: int, record_latency: bool):
+    def step(self, step_idx: int, record_latency: bool,
+             capture: bool = False):
         pods = [self.client.create_pod(
                     mixed_pod_spec(i, step_idx, self.rank,
                                    self.args.pod_pad_bytes))
                 for i in range(self.args.batch)]
+        if capture:
+            self._begin_capture(pods)
         if self.args.no_http:
             self._schedule_direct(pods, record_latency)
         elif self.args.kube_sim:
@@ -301,7 +326,62 @@ class BenchPipeline:
         else:
             self._schedule_http(pods, record_latency)
         self._verify_sample(pods)
+        if capture:
+            self._capture_placements(pods)
         self._release(pods)
+
+    # -- --dump-outputs: what a caller of the pipeline receives --
+
+    def _begin_capture(self, pods):
+        import numpy as np
+
+        b, n = len(pods), len(self.node_names)
+        self._capture_row = {p["metadata"]["uid"]: i
+                             for i, p in enumerate(pods)}
+        self._node_col = {name: j for j, name in enumerate(self.node_names)}
+        self._capture = {
+            # filter response: 1 where the node was returned as feasible
+            "feasible": np.zeros((b, n), dtype=np.float32),
+            # priorities response: score per feasible node, -1 elsewhere
+            "scores": np.full((b, n), -1.0, dtype=np.float32),
+            # bind result: index of the node the pod was bound to
+            "bound_node": np.full((b,), -1.0, dtype=np.float32),
+            # allocation annotation: 1 where a card was assigned to the pod
+            "cards": np.zeros((b, self.args.cards), dtype=np.float32),
+        }
+
+    def _record(self, pod, ok, score_by_host):
+        """Filter + priorities answers for one pod (a retry overwrites the
+        earlier attempt: the last answer is the one that was bound)."""
+        row = self._capture_row[pod["metadata"]["uid"]]
+        feas, scores = self._capture["feasible"], self._capture["scores"]
+        feas[row, :] = 0.0
+        scores[row, :] = -1.0
+        for host in ok:
+            feas[row, self._node_col[host]] = 1.0
+        for host, score in score_by_host.items():
+            scores[row, self._node_col[host]] = float(score)
+
+    def _capture_placements(self, pods):
+        from elastic_gpu_scheduler_amd.k8s import objects as obj
+
+        for i, pod in enumerate(pods):
+            bound = self.client.get_pod("default", pod["metadata"]["name"])
+            node = (bound.get("spec") or {}).get("nodeName")
+            if node in self._node_col:
+                self._capture["bound_node"][i] = float(self._node_col[node])
+            for per_container in obj.parse_allocation(bound) or []:
+                for card in per_container:
+                    self._capture["cards"][i, card] = 1.0
+
+    def dump_outputs(self, out_dir: str):
+        import numpy as np
+
+        if self._capture is None:
+            raise RuntimeError("--dump-outputs: no timed step was captured")
+        os.makedirs(out_dir, exist_ok=True)
+        for name, arr in self._capture.items():
+            np.save(os.path.join(out_dir, name + ".npy"), arr)
 
     def _schedule_http(self, pods, record_latency: bool):
         """Threaded load generator: each worker holds one keep-alive HTTP
@@ -354,7 +434,10 @@ class BenchPipeline:
                 "/scheduler/priorities", {"pod": pod, "nodenames": ok})
             top = max(e["score"] for e in prio)
             tied = [e["host"] for e in prio if e["score"] == top]
-            best = tied[(hash(pod["metadata"]["uid"]) + attempt) % len(tied)]
+            best = tied[(_tiebreak(pod["metadata"]["uid"]) + attempt)
+                        % len(tied)]
+            if self._capture is not None:
+                self._record(pod, ok, {e["host"]: e["score"] for e in prio})
             status, out = conn.post_json("/scheduler/bind", {
                 "podName": pod["metadata"]["name"],
                 "podNamespace": "default",
@@ -414,8 +497,11 @@ class BenchPipeline:
                         {"pod": pod, "nodenames": ok})
                     top = max(e["score"] for e in prio)
                     tied = [e["host"] for e in prio if e["score"] == top]
-                    node = tied[(hash(pod["metadata"]["uid"]) + attempt + 1)
-                                % len(tied)]
+                    node = tied[(_tiebreak(pod["metadata"]["uid"])
+                                 + attempt + 1) % len(tied)]
+                    if self._capture is not None:
+                        self._record(pod, ok,
+                                     {e["host"]: e["score"] for e in prio})
                 else:
                     errors.append(RuntimeError("bind kept failing"))
                     return
@@ -439,7 +525,10 @@ class BenchPipeline:
                     "/scheduler/priorities", {"pod": pod, "nodenames": ok})
                 top = max(e["score"] for e in prio)
                 tied = [e["host"] for e in prio if e["score"] == top]
-                best = tied[hash(pod["metadata"]["uid"]) % len(tied)]
+                best = tied[_tiebreak(pod["metadata"]["uid"]) % len(tied)]
+                if self._capture is not None:
+                    self._record(pod, ok,
+                                 {e["host"]: e["score"] for e in prio})
                 futures.append(binder.submit(do_bind, pod, best, t0))
             for f in futures:
                 f.result()
@@ -463,7 +552,10 @@ class BenchPipeline:
                 scores = sch.score(ok, pod)
                 top = max(scores)
                 tied = [n for n, s in zip(ok, scores) if s == top]
-                best = tied[(hash(pod["metadata"]["uid"]) + attempt) % len(tied)]
+                best = tied[(_tiebreak(pod["metadata"]["uid"]) + attempt)
+                            % len(tied)]
+                if self._capture is not None:
+                    self._record(pod, ok, dict(zip(ok, scores)))
                 try:
                     sch.bind(best, self.client.get_pod(
                         "default", pod["metadata"]["name"]))
@@ -490,7 +582,7 @@ class BenchPipeline:
                 continue
             # stamp on the local physical card (the bench box has 1 visible
             # card per rank; logical index maps onto it)
-            tag = hash(bound["metadata"]["uid"]) & ((1 << 64) - 1)
+            tag = uuid.UUID(bound["metadata"]["uid"]).int & ((1 << 64) - 1)
             if not self.probe.stamp(self.device_index, tag, 8):
                 raise RuntimeError("placement stamp verification failed")
             verified += 1
@@ -564,7 +656,17 @@ def main():
                         "model realistic (multi-kB) pod specs on the wire")
     p.add_argument("--verify-sample", type=int, default=2,
                    help="placements stamped on-device per step")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step computed (feasible nodes, scores, bound node, "
+                        "allocated cards per pod) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the extra measurements that are not part "
+                        "of the headline figure (measured xGMI topology on "
+                        "a multi-GPU box)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
 
     import torch
 
@@ -606,14 +708,15 @@ def main():
         with _quiet_stdout():
             dist.init_process_group(backend="nccl" if use_gpu else "gloo")
 
-    # Opportunistic multi-GPU topology capture (the
+    # --full only: multi-GPU topology capture (the
     # >=2-card branches of probe.hip had never seen hardware): when this
     # bench lands on a multi-GPU box (the driver's 8-GPU scaling run),
     # rank 0 measures the REAL xGMI hop matrix + p2p bandwidths once,
     # before the timed region, in a SUBPROCESS with a hard timeout so a
     # wedged p2p path can never hang the bench itself.
     xgmi_measured = None
-    if use_gpu and rank == 0 and torch.cuda.device_count() > 1:
+    if (args.full and use_gpu and rank == 0
+            and torch.cuda.device_count() > 1):
         import subprocess
         import sys as _sys
 
@@ -679,7 +782,9 @@ def main():
         for s in range(args.steps):
             if s == 1 and profile_thread is not None:
                 profile_thread.start()  # sample while under steady load
-            pipe.step(s, record_latency=True)
+            pipe.step(s, record_latency=True,
+                      capture=bool(args.dump_outputs)
+                      and s == args.steps - 1)
         barrier()
         elapsed = time.perf_counter() - t0
 
@@ -691,6 +796,9 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+
+        if args.dump_outputs and rank == 0:
+            pipe.dump_outputs(args.dump_outputs)
 
         if rank == 0:
             pods_total = args.batch * args.steps * world_size

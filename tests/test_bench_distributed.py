@@ -50,3 +50,39 @@ def test_bench_single_rank_json_contract():
         assert key in result, key
     assert result["n_gpus"] == 1
     assert result["data"] == "synthetic"
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's results as .npy, and the
+    same arguments give the same inputs, hence identical outputs, in two
+    separate processes (--full on one of them must not change them)."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out_dir = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, str(REPO / "bench.py"), "--steps", "3",
+             "--warmup", "1", "--batch", "16", "--no-verify",
+             "--dump-outputs", str(out_dir)] + extra,
+            capture_output=True, text=True, timeout=600, cwd=str(REPO))
+        assert out.returncode == 0, out.stderr[-3000:]
+        result = json.loads([l for l in out.stdout.splitlines()
+                             if l.startswith("{")][0])
+        assert result["steps"] == 3
+        assert result["ms_per_step"] > 0
+        dumps.append({p.stem: np.load(p) for p in out_dir.glob("*.npy")})
+    a, b = dumps
+    assert set(a) == {"feasible", "scores", "bound_node", "cards"}
+    assert set(b) == set(a)
+    for name, arr in a.items():
+        assert arr.dtype in (np.float32, np.float64), name
+        assert arr.shape[0] == 16, name
+        assert np.array_equal(arr, b[name]), name
+    # every pod was bound to a feasible node and holds at least one card
+    rows = np.arange(16)
+    nodes = a["bound_node"].astype(int)
+    assert (nodes >= 0).all()
+    assert (a["feasible"][rows, nodes] == 1).all()
+    assert (a["scores"][rows, nodes] >= 0).all()
+    assert (a["cards"].sum(axis=1) >= 1).all()
