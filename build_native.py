@@ -75,7 +75,7 @@ def build_gpuprobe(force: bool = False) -> Path | None:
         return None
     out = PKG / ("_gpuprobe" + _ext_suffix())
     sources = sorted(PROBE_SRC.glob("*.hip"))
-    if force or _needs_rebuild(out, sources):
+    if force or _needs_rebuild(out, sources + sorted(PROBE_SRC.glob("*.h"))):
         cmd = (
             [hipcc, f"--offload-arch={GFX_ARCH}", "-O3", "-std=c++17", "-shared",
              "-fPIC", "-fvisibility=hidden"]

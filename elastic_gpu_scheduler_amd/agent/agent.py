@@ -14,6 +14,8 @@ equivalent's control logic:
     published inventory;
   * health_check() — runs the HIP HBM-bandwidth probe per card and flags
     cards below a threshold (a sick HBM stack or wrong partition mode);
+  * self_test() — the deep, opt-in version: HBM pattern test, per-XCD read
+    bandwidth and an MFMA check per card, judged by agent/health.py;
   * verify_placement() — stamps a pod-unique tag on the cards a bound pod
     was assigned, proving the scheduler/device-plugin contract held
     (BASELINE.json: "rocprof/amd-smi spot-check that containers land on the
@@ -23,10 +25,12 @@ from __future__ import annotations
 
 import json
 import logging
+import time
 from typing import Any, Dict, List, Optional
 
 from elastic_gpu_scheduler_amd.agent import inventory as inv
 from elastic_gpu_scheduler_amd.agent import topology as topo
+from elastic_gpu_scheduler_amd.agent.health import HealthLimits, evaluate_card
 from elastic_gpu_scheduler_amd.k8s.client import KubeClient
 from elastic_gpu_scheduler_amd.utils import types as t
 
@@ -37,6 +41,10 @@ log = logging.getLogger("egs.agent")
 # partition and should not be scheduled onto.
 HBM_HEALTH_THRESHOLD_GBPS = 1000.0
 
+# Seed of the deep self-test's HBM pattern (any value serves; fixed so a
+# reported word index and XOR can be reproduced).
+SELF_TEST_PATTERN_SEED = 0x6A09E667F3BCC908
+
 
 class NodeAgent:
     def __init__(self, node_name: str, client: Optional[KubeClient] = None,
@@ -44,6 +52,8 @@ class NodeAgent:
         self.node_name = node_name
         self.client = client
         self.prefer_source = prefer_source
+        # cards the most recent deep self-test found unhealthy
+        self._deep_sick: set = set()
 
     # -- discovery --
 
@@ -87,17 +97,33 @@ class NodeAgent:
             pass  # client without status-subresource support
         return ann
 
-    def publish_with_health(self, mib: int = 256, iters: int = 5
-                            ) -> Dict[str, Any]:
+    def publish_with_health(self, mib: int = 256, iters: int = 5,
+                            deep: bool = False) -> Dict[str, Any]:
         """Publish inventory with unhealthy cards EXCLUDED (HBM bandwidth
         below threshold): the scheduler stops placing onto sick cards at the
         next node-cache refresh. Returns {"published": ann, "sick": [...]}.
+
+        deep=True gates on self_test() instead of the bandwidth probe alone
+        and also publishes the per-card verdicts as the
+        elasticgpu.io/gpu-health annotation. A card the last deep run found
+        bad stays excluded through the plain cycles in between: a bandwidth
+        probe cannot clear a data or matrix-core error.
         """
         if self.client is None:
             raise RuntimeError("publish_with_health needs a KubeClient")
-        report = self.health_check(mib=mib, iters=iters)
+        if deep:
+            report = self.self_test()
+            self._deep_sick = {r["index"] for r in report if not r["healthy"]}
+        else:
+            report = self.health_check(mib=mib, iters=iters)
         sick = [r["index"] for r in report if not r["healthy"]]
+        if not deep and self._deep_sick:
+            sick = sorted(set(sick) | self._deep_sick)
         ann = self.annotations()
+        if deep:
+            ann[t.ANNOTATION_NODE_HEALTH] = json.dumps(
+                {"cards": [health_summary(r) for r in report]},
+                separators=(",", ":"))
         inv = json.loads(ann[t.ANNOTATION_NODE_INVENTORY])
         # Sick cards stay in the list as zero-capacity placeholders so list
         # position keeps equalling the PHYSICAL card index — dropping an
@@ -147,6 +173,44 @@ class NodeAgent:
                         "healthy": bw >= HBM_HEALTH_THRESHOLD_GBPS})
         return out
 
+    def self_test(self, pattern_mib: int = 1024, slice_mib: int = 128,
+                  mfma_iters: int = 256) -> List[Dict[str, Any]]:
+        """Deep per-card self-test: the bandwidth probe plus the HBM pattern
+        test, per-XCD read bandwidth and the MFMA check. One report per card:
+        {index, hbm_gbps, pattern, xcd, mfma, healthy, reasons}.
+
+        The defaults are the health settings: a pattern buffer must be well
+        above the 256 MiB Infinity Cache for its verify pass to read HBM
+        cells (smaller sizes only test the kernels and the caches), and
+        8 x 128 MiB of XCD slices stream from HBM for the same reason. A run
+        allocates about 1 GiB at a time on the card and saturates it for a
+        moment, so it is not something to run every cycle next to tenants.
+        """
+        from elastic_gpu_scheduler_amd._native import gpuprobe
+
+        probe = gpuprobe()
+        slice_mib = slice_mib if 0 < slice_mib <= 512 else 128
+        slice_words = slice_mib * 1024 * 1024 // 8
+        chunk_kib = 256
+        limits = HealthLimits(hbm_gbps=HBM_HEALTH_THRESHOLD_GBPS)
+        out = []
+        for i in range(probe.device_count()):
+            report: Dict[str, Any] = {
+                "index": i,
+                "hbm_gbps": probe.hbm_bandwidth(i, 256, 5),
+                "pattern": probe.hbm_pattern_test(
+                    i, pattern_mib * 1024 * 1024, SELF_TEST_PATTERN_SEED),
+                "xcd": _xcd_or_skipped(probe, i, slice_mib, chunk_kib),
+                "mfma": probe.mfma_selftest(i, mfma_iters),
+            }
+            for e in ([] if "skipped" in report["xcd"] else report["xcd"]):
+                e["expected_chunks"] = slice_mib * 1024 // chunk_kib
+                e["expected_checksum"] = probe.pattern_xor(
+                    probe.XCD_PATTERN_SEED, e["xcc"] * slice_words, slice_words)
+            report.update(evaluate_card(report, limits))
+            out.append(report)
+        return out
+
     def verify_placement(self, pod_uid: str, device_indexes: List[int],
                          mib: int = 16) -> bool:
         """Stamp+verify a pod-unique pattern on each assigned card."""
@@ -170,6 +234,38 @@ class NodeAgent:
                 if i != j:
                     bw[i][j] = probe.p2p_bandwidth(i, j, mib, iters)
         return {"hops": probe.xgmi_hop_matrix(), "bandwidth_gbps": bw}
+
+
+def _xcd_or_skipped(probe, device: int, slice_mib: int, chunk_kib: int):
+    """xcd_bandwidth, with its refusal to allocate on a full card turned
+    into a skipped sub-report (like hbm_pattern_test's) instead of failing
+    the whole cycle."""
+    try:
+        return probe.xcd_bandwidth(device, slice_mib, 3, chunk_kib)
+    except RuntimeError as exc:
+        if "insufficient free device memory" not in str(exc):
+            raise
+        return {"skipped": "insufficient free memory"}
+
+
+def health_summary(report: Dict[str, Any]) -> Dict[str, Any]:
+    """One card's entry of the gpu-health annotation: the verdict and the
+    figures behind it, without the raw mismatch records."""
+    pattern = report.get("pattern") or {}
+    xcd = report.get("xcd") or []
+    return {
+        "index": report["index"],
+        "healthy": report["healthy"],
+        "reasons": report["reasons"],
+        "hbm_gbps": round(report.get("hbm_gbps", 0.0), 1),
+        "xcd_gbps": {str(e["xcc"]): round(e["gbps"], 1)
+                     for e in ([] if "skipped" in xcd else xcd)},
+        "hbm_mismatches": (None if "skipped" in pattern
+                           else list(pattern.get("mismatches", []))),
+        "mfma_mismatches": sum(e.get("mismatched_elements", 0)
+                               for e in report.get("mfma") or []),
+        "ts": int(time.time()),
+    }
 
 
 def _uid_tag(uid: str) -> int:

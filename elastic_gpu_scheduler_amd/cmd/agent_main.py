@@ -12,7 +12,9 @@ Publishes:
   elasticgpu.io/xgmi-topology   hop matrix for locality-aware placement
 and optionally runs the HBM health probe each cycle, publishing sick cards
 as zero-capacity placeholders (list position always equals the physical card
-index) so the scheduler stops placing pods on them.
+index) so the scheduler stops placing pods on them. --self-test adds the deep
+per-card self-test every Nth cycle and publishes its verdicts as
+  elasticgpu.io/gpu-health      per-card {healthy, reasons, figures}
 """
 from __future__ import annotations
 
@@ -33,6 +35,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--health-check", action="store_true",
                    help="run the HBM bandwidth probe each cycle and exclude "
                         "unhealthy cards from the inventory")
+    p.add_argument("--self-test", action="store_true",
+                   help="gate on the deep self-test (HBM pattern, per-XCD "
+                        "bandwidth, MFMA check) as well; implies --health-check")
+    p.add_argument("--self-test-every", type=int, default=12, metavar="N",
+                   help="with --self-test: run the deep test on the first "
+                        "cycle and every Nth after, the plain health check in "
+                        "between (a deep run allocates about 1 GiB per card "
+                        "and saturates it for a moment)")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -66,9 +76,15 @@ def main(argv=None) -> int:
     client = RealKubeClient.from_env()
     agent = NodeAgent(args.node, client, prefer_source=args.source)
 
+    cycle = 0
     while True:
         try:
-            if args.health_check:
+            if args.self_test and cycle % max(args.self_test_every, 1) == 0:
+                out = agent.publish_with_health(deep=True)
+                if out["sick"]:
+                    log.warning("self-test failed (published zero-capacity): %s",
+                                out["sick"])
+            elif args.health_check or args.self_test:
                 out = agent.publish_with_health()
                 if out["sick"]:
                     log.warning("unhealthy cards (published zero-capacity): %s",
@@ -78,6 +94,7 @@ def main(argv=None) -> int:
             log.info("published inventory for %s", args.node)
         except Exception:
             log.exception("publish failed; retrying next cycle")
+        cycle += 1
         if args.interval <= 0:
             return 0
         time.sleep(args.interval)

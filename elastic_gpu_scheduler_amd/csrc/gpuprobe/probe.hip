@@ -12,6 +12,8 @@
 //   * stamp — writes a pod-unique pattern into a small device allocation and
 //     verifies it, proving a bound pod's container really landed on the card
 //     indexes the scheduler chose (placement verification).
+// The deep card self-test (HBM pattern, per-XCD bandwidth, MFMA check) lives
+// in selftest.hip and registers into this module.
 //
 // All entry points are bounded in memory and time; kernels are trivial
 // streaming loops sized with grid-stride so any buffer size fills the chip
@@ -27,16 +29,9 @@
 #include <utility>
 #include <vector>
 
-namespace py = pybind11;
+#include "common.h"
 
-#define HIP_CHECK(expr)                                                        \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      throw std::runtime_error(std::string("HIP error at " #expr ": ") +       \
-                               hipGetErrorString(_e));                         \
-    }                                                                          \
-  } while (0)
+namespace py = pybind11;
 
 namespace {
 
@@ -81,7 +76,9 @@ std::pair<int, std::string> hip_status() {
   return {e == hipSuccess ? n : -1, hipGetErrorString(e)};
 }
 
-void require_device(int device) {
+}  // namespace
+
+void gpuprobe::require_device(int device) {
   int n = checked_device_count();
   if (device < 0 || device >= n)
     throw std::runtime_error("device index " + std::to_string(device) +
@@ -89,7 +86,7 @@ void require_device(int device) {
   HIP_CHECK(hipSetDevice(device));
 }
 
-}  // namespace
+using gpuprobe::require_device;
 
 static py::dict device_info(int device) {
   require_device(device);
@@ -275,4 +272,5 @@ PYBIND11_MODULE(_gpuprobe, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("stamp", &stamp, py::arg("device") = 0, py::arg("tag") = 0,
         py::arg("mib") = 16, py::call_guard<py::gil_scoped_release>());
+  register_selftest(m);
 }

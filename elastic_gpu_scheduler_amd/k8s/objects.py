@@ -250,6 +250,27 @@ def node_devices(node: Node, bare_unit: str = "auto") -> List[Any]:
     return []
 
 
+def node_card_health(node: Node) -> Dict[int, List[str]]:
+    """Cards the agent's deep self-test found unhealthy, as {physical index:
+    [reasons]} from the elasticgpu.io/gpu-health annotation. Empty when the
+    annotation is absent or malformed: it explains a zero-capacity card, it
+    never decides schedulability (the inventory does)."""
+    import json
+
+    ann = (node.get("metadata", {}) or {}).get("annotations", {}) or {}
+    raw = ann.get(t.ANNOTATION_NODE_HEALTH)
+    if not raw:
+        return {}
+    try:
+        out: Dict[int, List[str]] = {}
+        for card in json.loads(raw)["cards"]:
+            if not card["healthy"]:
+                out[int(card["index"])] = [str(r) for r in card["reasons"]]
+        return out
+    except (ValueError, TypeError, KeyError, AttributeError):
+        return {}
+
+
 def node_topology(node: Node) -> List[List[int]]:
     """Agent-published xGMI hop matrix; empty = assume a single fully
     connected hive (every MI355X OAM pair is one xGMI hop)."""

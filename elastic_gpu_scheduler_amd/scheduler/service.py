@@ -56,6 +56,9 @@ class GPUUnitScheduler:
         # fast-path membership cache over state's node map (adds only; a
         # removed node falls back to the authoritative native check)
         self._known_nodes: set = set()
+        # per cached node: {card index: [reasons]} from the agent's
+        # gpu-health annotation (observability only; status())
+        self._card_health: Dict[str, Dict[int, List[str]]] = {}
         # Binds in flight per node + deferred invalidations: evicting a
         # node between a bind's in-memory allocate and its annotation
         # write would lose the reservation — the refill replays only
@@ -122,6 +125,7 @@ class GPUUnitScheduler:
                 return False
             topo = obj.node_topology(node)
             self.state.add_node(node_name, devices, topo)
+            self._card_health[node_name] = obj.node_card_health(node)
             if replay:
                 try:
                     pods = self.client.list_pods(
@@ -153,6 +157,7 @@ class GPUUnitScheduler:
     def _evict_node(self, node_name: str) -> None:
         with self._fill_mu:  # atomic vs any in-progress refill
             self._known_nodes.discard(node_name)
+            self._card_health.pop(node_name, None)
             self.state.remove_node(node_name)
 
     def _bind_enter(self, node_name: str) -> None:
@@ -346,6 +351,9 @@ class GPUUnitScheduler:
                 } for d in devices],
                 "pods": self.state.node_pod_placements(name),
             }
+            unhealthy = self._card_health.get(name)
+            if unhealthy:
+                nodes[name]["unhealthy_cards"] = dict(unhealthy)
         return {"name": self.name, "policy": self.policy, "nodes": nodes}
 
     def _emit_event(self, pod: Dict[str, Any], reason: str, message: str) -> None:

@@ -44,6 +44,7 @@ ANNOTATION_EGPU_SCORE = "elasticgpu.io/placement-score"
 # Node-side annotations published by the MI355X agent:
 ANNOTATION_NODE_TOPOLOGY = "elasticgpu.io/xgmi-topology"  # JSON hop matrix
 ANNOTATION_NODE_INVENTORY = "elasticgpu.io/gpu-inventory"  # JSON per-card info
+ANNOTATION_NODE_HEALTH = "elasticgpu.io/gpu-health"  # JSON deep self-test verdicts
 
 # --- Scheduling policies ---
 PRIORITY_BINPACK = "binpack"
