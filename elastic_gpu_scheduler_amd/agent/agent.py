@@ -19,7 +19,13 @@ equivalent's control logic:
   * verify_placement() — stamps a pod-unique tag on the cards a bound pod
     was assigned, proving the scheduler/device-plugin contract held
     (BASELINE.json: "rocprof/amd-smi spot-check that containers land on the
-    chosen card indices" — this is the programmatic version).
+    chosen card indices" — this is the programmatic version);
+  * assign_masks() / sync_masks() / verify_masks() — gpu-core enforcement:
+    each fractional container gets a CU mask sized to its share
+    (agent/cumask.py), recorded on the pod as elasticgpu.io/cu-mask and
+    turned into the container's environment by agent/wiring.py;
+    verify_masks() proves on the card that the masks confine work to
+    disjoint physical CUs.
 """
 from __future__ import annotations
 
@@ -30,7 +36,11 @@ from typing import Any, Dict, List, Optional
 
 from elastic_gpu_scheduler_amd.agent import inventory as inv
 from elastic_gpu_scheduler_amd.agent import topology as topo
+from elastic_gpu_scheduler_amd.agent.cumask import (CardMaskPlan, MaskGrant,
+                                                    mask_hex, parse_mask_hex)
 from elastic_gpu_scheduler_amd.agent.health import HealthLimits, evaluate_card
+from elastic_gpu_scheduler_amd.agent.wiring import fractional_core, pod_cu_masks
+from elastic_gpu_scheduler_amd.k8s import objects as obj
 from elastic_gpu_scheduler_amd.k8s.client import KubeClient
 from elastic_gpu_scheduler_amd.utils import types as t
 
@@ -54,6 +64,10 @@ class NodeAgent:
         self.prefer_source = prefer_source
         # cards the most recent deep self-test found unhealthy
         self._deep_sick: set = set()
+        # CU-mask state: measured layouts, one plan per card, entries per pod
+        self._mask_layouts: Optional[Dict[int, Dict[str, Any]]] = None
+        self._mask_plans: Dict[int, CardMaskPlan] = {}
+        self._pod_masks: Dict[str, Dict[str, Dict[str, Any]]] = {}
 
     # -- discovery --
 
@@ -234,6 +248,173 @@ class NodeAgent:
                 if i != j:
                     bw[i][j] = probe.p2p_bandwidth(i, j, mib, iters)
         return {"hops": probe.xgmi_hop_matrix(), "bandwidth_gbps": bw}
+
+    # -- gpu-core enforcement: per-container CU masks --
+
+    def mask_layouts(self) -> Dict[int, Dict[str, Any]]:
+        """How CU-mask bits map to XCDs on each card (the probe's
+        cu_mask_layout), measured once and cached."""
+        if self._mask_layouts is None:
+            from elastic_gpu_scheduler_amd._native import gpuprobe
+
+            probe = gpuprobe()
+            self._mask_layouts = {i: probe.cu_mask_layout(i)
+                                  for i in range(probe.device_count())}
+        return self._mask_layouts
+
+    def mask_plan(self, card: int) -> Optional[CardMaskPlan]:
+        """The card's mask plan; None when its layout is unknown or not
+        interleaved: no masks are planned for such a card."""
+        plan = self._mask_plans.get(card)
+        if plan is None:
+            layout = self.mask_layouts().get(card)
+            if not layout or not layout.get("interleaved"):
+                return None
+            plan = CardMaskPlan(int(layout["cus"]), int(layout["granule"]))
+            self._mask_plans[card] = plan
+        return plan
+
+    def assign_masks(self, pod: Dict[str, Any]) -> Dict[str, Dict[str, Any]]:
+        """Grant a CU mask to each fractional container of a placed pod:
+        {container: {card, mask, cus, shared}}. Idempotent per pod uid. Masks
+        the pod's annotation already records are adopted as they are (its
+        containers may be running under them); otherwise new ones are
+        granted and, with a client, written to the pod as the
+        elasticgpu.io/cu-mask annotation."""
+        uid = obj.pod_uid(pod)
+        if uid in self._pod_masks:
+            return self._pod_masks[uid]
+        allocation = obj.parse_allocation(pod)
+        if allocation is None:
+            return {}
+        recorded = pod_cu_masks(pod)
+        entries: Dict[str, Dict[str, Any]] = {}
+        containers = pod.get("spec", {}).get("containers", []) or []
+        for i, c in enumerate(containers):
+            name = c.get("name", str(i))
+            share = fractional_core(c)
+            if not share or len(allocation[i]) != 1:
+                continue
+            plan = self.mask_plan(allocation[i][0])
+            if plan is None:
+                continue
+            key = f"{uid}/{name}"
+            old = recorded.get(name)
+            if old is not None and old["card"] == allocation[i][0]:
+                try:
+                    plan.restore({key: MaskGrant(parse_mask_hex(old["mask"]),
+                                                 old["cus"], old["shared"])})
+                except ValueError:
+                    log.warning("pod %s: unusable recorded cu-mask %r",
+                                obj.pod_key(pod), old["mask"])
+                    continue
+                grant = plan.grants()[key]
+            else:
+                grant = plan.allocate(key, share)
+            entries[name] = {"card": allocation[i][0],
+                             "mask": mask_hex(grant.mask),
+                             "cus": grant.cus, "shared": grant.shared}
+        if not entries:
+            return {}
+        self._pod_masks[uid] = entries
+        if self.client is not None and entries != recorded:
+            try:
+                self._write_mask_annotation(pod, entries)
+            except Exception:
+                self.release_masks(uid)  # nothing was promised to anyone yet
+                raise
+        return entries
+
+    def _write_mask_annotation(self, pod: Dict[str, Any],
+                               entries: Dict[str, Dict[str, Any]]) -> None:
+        from elastic_gpu_scheduler_amd.k8s.client import ConflictError
+
+        raw = json.dumps(entries, separators=(",", ":"), sort_keys=True)
+        for attempt in range(3):
+            fresh = self.client.get_pod(obj.pod_namespace(pod), obj.pod_name(pod))
+            fresh.setdefault("metadata", {}).setdefault(
+                "annotations", {})[t.ANNOTATION_POD_CU_MASK] = raw
+            try:
+                self.client.update_pod(fresh)
+                return
+            except ConflictError:
+                if attempt == 2:
+                    raise
+
+    def release_masks(self, pod_uid: str) -> None:
+        for name, e in self._pod_masks.pop(pod_uid, {}).items():
+            plan = self._mask_plans.get(e["card"])
+            if plan is not None:
+                plan.release(f"{pod_uid}/{name}")
+
+    def sync_masks(self) -> Dict[str, Dict[str, Dict[str, Any]]]:
+        """Bring the plans in line with the pods placed on this node: adopt
+        the masks existing annotations record first, then grant masks to the
+        pods that have none, then free those of pods that are gone or
+        completed. Returns {pod uid: mask entries}."""
+        if self.client is None:
+            raise RuntimeError("NodeAgent.sync_masks needs a KubeClient")
+        live = []
+        for pod in self.client.list_pods():
+            ann = pod.get("metadata", {}).get("annotations", {}) or {}
+            if (ann.get(t.ANNOTATION_EGPU_NODE) == self.node_name
+                    and not obj.is_completed_pod(pod)):
+                live.append(pod)
+        live.sort(key=lambda p: (obj.pod_key(p), obj.pod_uid(p)))
+        for recorded_first in (True, False):
+            for pod in live:
+                if bool(pod_cu_masks(pod)) == recorded_first:
+                    self.assign_masks(pod)
+        uids = {obj.pod_uid(p) for p in live}
+        for uid in [u for u in self._pod_masks if u not in uids]:
+            self.release_masks(uid)
+        return dict(self._pod_masks)
+
+    def verify_masks(self, card: int) -> Dict[str, Any]:
+        """Run the occupancy probe under every grant on `card`. Each grant
+        must show as many physical CUs as its mask has bits, equally many on
+        every XCD, and grants not marked shared must be pairwise disjoint in
+        physical CUs. Returns {"ok", "overlaps", "per_grant"}. Nothing is
+        launched under a mask on a card whose layout is not interleaved, or
+        under a mask that is not whole granules."""
+        from elastic_gpu_scheduler_amd._native import gpuprobe
+
+        layout = self.mask_layouts().get(card)
+        plan = self.mask_plan(card)
+        if not layout or plan is None:
+            return {"ok": False, "reason": "unsupported-layout"}
+        probe = gpuprobe()
+        xccs = int(layout["xccs"])
+        seen: Dict[Any, set] = {}
+        per_grant: Dict[Any, Dict[str, Any]] = {}
+        grants = plan.grants()
+        for key, grant in grants.items():
+            if not plan.whole_granules(grant.mask):
+                per_grant[key] = {"ok": False, "reason": "not-whole-granules"}
+                continue
+            occ = probe.cu_occupancy(card, mask=grant.mask)
+            cus = {(e["xcc"], e["se"], e["sh"], e["cu"]) for e in occ["cus"]}
+            per_xcc: Dict[int, int] = {}
+            for k in cus:
+                per_xcc[k[0]] = per_xcc.get(k[0], 0) + 1
+            seen[key] = cus
+            per_grant[key] = {
+                "ok": (occ["applied_mask"] == grant.mask
+                       and len(cus) == grant.cus and len(per_xcc) == xccs
+                       and set(per_xcc.values()) == {grant.cus // xccs}),
+                "mask": mask_hex(grant.mask), "cus": len(cus),
+                "per_xcc": dict(sorted(per_xcc.items())),
+                "shared": grant.shared,
+            }
+        overlaps = []
+        keys = [k for k in seen if not grants[k].shared]
+        for i, a in enumerate(keys):
+            for b in keys[i + 1:]:
+                both = seen[a] & seen[b]
+                if both:
+                    overlaps.append({"a": a, "b": b, "cus": sorted(both)})
+        return {"ok": not overlaps and all(g["ok"] for g in per_grant.values()),
+                "overlaps": overlaps, "per_grant": per_grant}
 
 
 def _xcd_or_skipped(probe, device: int, slice_mib: int, chunk_kib: int):

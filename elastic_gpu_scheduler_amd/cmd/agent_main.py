@@ -15,6 +15,9 @@ as zero-capacity placeholders (list position always equals the physical card
 index) so the scheduler stops placing pods on them. --self-test adds the deep
 per-card self-test every Nth cycle and publishes its verdicts as
   elasticgpu.io/gpu-health      per-card {healthy, reasons, figures}
+--cu-masks enforces gpu-core: every fractional container placed on this node
+is granted a CU mask sized to its share, recorded on the pod as
+  elasticgpu.io/cu-mask         per-container {card, mask, cus, shared}
 """
 from __future__ import annotations
 
@@ -43,6 +46,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "cycle and every Nth after, the plain health check in "
                         "between (a deep run allocates about 1 GiB per card "
                         "and saturates it for a moment)")
+    p.add_argument("--cu-masks", action="store_true",
+                   help="enforce gpu-core: each cycle grant a CU mask to every "
+                        "fractional container placed on this node and record "
+                        "it as the pod's elasticgpu.io/cu-mask annotation")
+    p.add_argument("--cu-mask-layout", action="store_true",
+                   help="measure how CU-mask bits map to XCDs on each card, "
+                        "print it as JSON and exit")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -60,6 +70,12 @@ def main(argv=None) -> int:
     log = logging.getLogger("egs.agent.main")
 
     from elastic_gpu_scheduler_amd.agent.agent import NodeAgent
+
+    if args.cu_mask_layout:
+        agent = NodeAgent(args.node or "local", client=None,
+                          prefer_source=args.source)
+        print(json.dumps(agent.mask_layouts(), indent=2))
+        return 0
 
     if args.dry_run:
         agent = NodeAgent(args.node or "dry-run-node", client=None,
@@ -94,6 +110,12 @@ def main(argv=None) -> int:
             log.info("published inventory for %s", args.node)
         except Exception:
             log.exception("publish failed; retrying next cycle")
+        if args.cu_masks:
+            try:
+                masks = agent.sync_masks()
+                log.info("cu masks held by %d pods", len(masks))
+            except Exception:
+                log.exception("cu-mask sync failed; retrying next cycle")
         cycle += 1
         if args.interval <= 0:
             return 0

@@ -1,4 +1,5 @@
-// Shared between the probe's translation units (probe.hip, selftest.hip).
+// Shared between the probe's translation units (probe.hip, selftest.hip,
+// cumask.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,3 +27,6 @@ void require_device(int device);
 
 // Adds the deep self-test entry points (selftest.hip) to the module.
 void register_selftest(pybind11::module_& m);
+
+// Adds the CU-mask probes (cumask.hip) to the module.
+void register_cumask(pybind11::module_& m);

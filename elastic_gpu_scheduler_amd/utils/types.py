@@ -41,6 +41,10 @@ ANNOTATION_SPREAD_CONTAINERS = "elasticgpu.io/spread-containers"
 # MI355X-native extensions (ours; absent on reference-scheduled pods):
 ANNOTATION_EGPU_NODE = "elasticgpu.io/scheduled-node"
 ANNOTATION_EGPU_SCORE = "elasticgpu.io/placement-score"
+# Written onto the pod by the node agent: the CU mask each fractional
+# container must be started under. JSON,
+# {"<container>": {"card": 2, "mask": "0x...", "cus": 64, "shared": false}}.
+ANNOTATION_POD_CU_MASK = "elasticgpu.io/cu-mask"
 # Node-side annotations published by the MI355X agent:
 ANNOTATION_NODE_TOPOLOGY = "elasticgpu.io/xgmi-topology"  # JSON hop matrix
 ANNOTATION_NODE_INVENTORY = "elasticgpu.io/gpu-inventory"  # JSON per-card info
