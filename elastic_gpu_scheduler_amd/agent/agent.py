@@ -25,7 +25,10 @@ equivalent's control logic:
     (agent/cumask.py), recorded on the pod as elasticgpu.io/cu-mask and
     turned into the container's environment by agent/wiring.py;
     verify_masks() proves on the card that the masks confine work to
-    disjoint physical CUs.
+    disjoint physical CUs;
+  * verify_isolation() — a qualification run for an idle card: two tenants
+    in separate processes under disjoint masks, each one's rate alone and
+    next to the other (agent/cotenancy.py).
 """
 from __future__ import annotations
 
@@ -415,6 +418,48 @@ class NodeAgent:
                     overlaps.append({"a": a, "b": b, "cus": sorted(both)})
         return {"ok": not overlaps and all(g["ok"] for g in per_grant.values()),
                 "overlaps": overlaps, "per_grant": per_grant}
+
+    def verify_isolation(self, card: int, shares=(50, 50),
+                         **window: Any) -> Dict[str, Any]:
+        """Two tenants holding `shares` percent of `card`, run as separate
+        processes under the masks the planner would grant them, exactly as
+        containers are wired: each tenant's FMA and HBM-stream rate alone and
+        while the other runs (cotenancy.isolation_report, to which `window`
+        is passed: pairs, launches, iters, bytes, passes, timeout). Returns
+        that report plus "tenants": [{core, mask, cus}].
+
+        The masks come from a scratch plan over the measured layout; the
+        live plan is not touched. As in verify_masks, nothing is launched
+        when the layout is unknown or not interleaved, or under a mask that
+        is not whole granules ("unsupported-layout"); shares that cannot
+        both be met from free granules are refused ("shares-overlap").
+
+        This is a qualification run for an idle card: it saturates the card
+        for about a second per pair and would itself be the noisy neighbour
+        of any tenant running there. "ok" says the measurement is valid, not
+        that the tenants are isolated."""
+        from elastic_gpu_scheduler_amd.agent import cotenancy
+
+        if len(shares) != 2:
+            raise ValueError("verify_isolation takes two shares")
+        layout = self.mask_layouts().get(card)
+        if not layout or not layout.get("interleaved"):
+            return {"ok": False, "reason": "unsupported-layout"}
+        try:
+            plan = CardMaskPlan(int(layout["cus"]), int(layout["granule"]))
+        except ValueError:
+            return {"ok": False, "reason": "unsupported-layout"}
+        grants = [plan.allocate(i, int(core)) for i, core in enumerate(shares)]
+        if not all(plan.whole_granules(g.mask) for g in grants):
+            return {"ok": False, "reason": "unsupported-layout"}
+        tenants = [{"core": int(core), "mask": mask_hex(g.mask), "cus": g.cus}
+                   for core, g in zip(shares, grants)]
+        if any(g.shared for g in grants) or grants[0].mask & grants[1].mask:
+            return {"ok": False, "reason": "shares-overlap", "tenants": tenants}
+        report = cotenancy.isolation_report(
+            card, [{"mask": g.mask} for g in grants], **window)
+        report["tenants"] = tenants
+        return report
 
 
 def _xcd_or_skipped(probe, device: int, slice_mib: int, chunk_kib: int):

@@ -1,0 +1,414 @@
+"""Two tenants on one card at once: does a gpu-core share keep its rate while
+the neighbour runs? (No GPU import at module level.)
+
+Each tenant is a fresh child process started the way a container is wired:
+the inherited environment plus ROC_GLOBAL_CU_MASK. A child runs the probe's
+cu_tenant_run, whose launches are stamped with the card's constant-rate wall
+clock. That clock is the same for every process on the card, so the parent
+can lay the two children's launches side by side afterwards and keep only
+those that provably ran while the other tenant was running:
+
+  * overlap()          — per launch of A, the fraction covered by B's launches;
+  * run_pair()         — up to two children at once, READY / GO handshake;
+  * isolation_report() — solo rates first, then the pairs, then the ratios.
+
+Concurrency comes from processes only: each child has one stream, and no
+child is ever started after one has failed.
+
+Child side: python -m elastic_gpu_scheduler_amd.agent.cotenancy --child ...
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import queue
+import statistics
+import subprocess
+import sys
+import threading
+import time
+from pathlib import Path
+from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
+
+from elastic_gpu_scheduler_amd.agent.cumask import mask_hex
+from elastic_gpu_scheduler_amd.agent.wiring import ENV_CU_MASK
+
+KINDS = ("fma", "stream")
+ALL_PAIRS: Tuple[Tuple[str, str], ...] = (
+    ("fma", "fma"), ("stream", "stream"), ("fma", "stream"), ("stream", "fma"))
+
+# A launch counts as contended when at least this much of it lies inside the
+# other tenant's launches: the few microseconds between two back-to-back
+# launches of the neighbour must not disqualify it.
+CONTENDED_FRACTION = 0.95
+# Never compute a ratio from fewer contended launches than this.
+MIN_CONTENDED = 3
+MAX_LAUNCHES = 64  # the probe's own cap
+CHILD_MODULE = "elastic_gpu_scheduler_amd.agent.cotenancy"
+
+Launches = Sequence[Mapping[str, Any]]
+
+
+# --- overlap ----------------------------------------------------------------
+
+def _union(launches: Launches) -> List[Tuple[int, int]]:
+    """The launches' [t0, t1] intervals, sorted and merged."""
+    merged: List[Tuple[int, int]] = []
+    for t0, t1 in sorted((int(l["t0"]), int(l["t1"])) for l in launches):
+        if t1 <= t0:
+            continue
+        if merged and t0 <= merged[-1][1]:
+            merged[-1] = (merged[-1][0], max(merged[-1][1], t1))
+        else:
+            merged.append((t0, t1))
+    return merged
+
+
+def overlap(launches_a: Launches, launches_b: Launches) -> List[Dict[str, Any]]:
+    """For each launch of A: {"fraction", "label"}. fraction is the part of
+    [t0, t1] covered by the union of B's launch intervals; label is
+    "contended" (fraction >= 0.95), "solo" (nothing covered) or "mixed"
+    (anything else, an empty interval included). Mixed launches count for
+    no rate."""
+    other = _union(launches_b)
+    out = []
+    for l in launches_a:
+        t0, t1 = int(l["t0"]), int(l["t1"])
+        if t1 <= t0:
+            out.append({"fraction": 0.0, "label": "mixed"})
+            continue
+        covered = sum(max(0, min(t1, b1) - max(t0, b0)) for b0, b1 in other)
+        fraction = covered / (t1 - t0)
+        label = ("contended" if fraction >= CONTENDED_FRACTION
+                 else "solo" if covered == 0 else "mixed")
+        out.append({"fraction": fraction, "label": label})
+    return out
+
+
+# --- child ------------------------------------------------------------------
+
+def _child_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="cotenancy", description=__doc__)
+    p.add_argument("--child", action="store_true", required=True)
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("--kind", choices=KINDS, default="fma")
+    p.add_argument("--launches", type=int, default=8)
+    p.add_argument("--iters", type=int, default=0)
+    p.add_argument("--bytes", type=int, default=0)
+    p.add_argument("--passes", type=int, default=0)
+    p.add_argument("--seed", type=int, default=1)
+    return p
+
+
+def child_main(argv: Optional[Sequence[str]] = None, stdin=None, stdout=None) -> int:
+    """One tenant: warm up, say READY, wait for GO, run, print TENANT <json>.
+    The CU mask is whatever ROC_GLOBAL_CU_MASK this process was started
+    under, so the probe is given a plain stream."""
+    args = _child_parser().parse_args(argv)
+    stdin = sys.stdin if stdin is None else stdin
+    stdout = sys.stdout if stdout is None else stdout
+    from elastic_gpu_scheduler_amd._native import gpuprobe
+
+    probe = gpuprobe()
+    window = {"kind": args.kind, "iters": args.iters, "bytes": args.bytes,
+              "passes": args.passes, "seed": args.seed}
+    warm = probe.cu_tenant_run(args.device, None, launches=1, **window)
+    if "skipped" in warm:
+        print(f"cotenancy child: {warm}", file=sys.stderr)
+        return 4
+    print("READY", file=stdout, flush=True)
+    if stdin.readline().strip() != "GO":
+        return 3
+    result = probe.cu_tenant_run(args.device, None, launches=args.launches, **window)
+    print("TENANT " + json.dumps(result), file=stdout, flush=True)
+    return 0
+
+
+# --- parent -----------------------------------------------------------------
+
+def _spawn(argv: List[str], env: Dict[str, str]):
+    """A fresh process, never exec: the parent may hold the GPU."""
+    return subprocess.Popen(argv, env=env, stdin=subprocess.PIPE,
+                            stdout=subprocess.PIPE, text=True)
+
+
+class _Trouble(Exception):
+    pass
+
+
+class _Child:
+    """One started tenant: its output lines arrive through a reader thread,
+    so that every wait on it ends at the child's own deadline."""
+
+    def __init__(self, index: int, proc, timeout: float) -> None:
+        self.index = index
+        self.proc = proc
+        self.deadline = time.monotonic() + timeout
+        self.lines: "queue.Queue[Optional[str]]" = queue.Queue()
+        threading.Thread(target=self._pump, daemon=True).start()
+
+    def _pump(self) -> None:
+        try:
+            for line in self.proc.stdout:
+                self.lines.put(line)
+        finally:
+            self.lines.put(None)
+
+    def _fail(self, what: str) -> _Trouble:
+        return _Trouble({"tenant": self.index, "what": what,
+                         "returncode": self.proc.poll()})
+
+    def expect(self, prefix: str) -> str:
+        while True:
+            left = self.deadline - time.monotonic()
+            try:
+                if left <= 0:
+                    raise queue.Empty
+                line = self.lines.get(timeout=left)
+            except queue.Empty:
+                raise self._fail(f"timed out waiting for {prefix}") from None
+            if line is None:
+                try:  # the exit status belongs in the detail
+                    self.proc.wait(timeout=max(self.deadline - time.monotonic(), 0.1))
+                except subprocess.TimeoutExpired:
+                    pass
+                raise self._fail(f"no {prefix} line")
+            if line.startswith(prefix):
+                return line[len(prefix):].strip()
+
+    def go(self) -> None:
+        try:
+            self.proc.stdin.write("GO\n")
+            self.proc.stdin.flush()
+        except (OSError, ValueError):
+            raise self._fail("could not be told GO") from None
+
+    def finish(self) -> None:
+        try:
+            code = self.proc.wait(timeout=max(self.deadline - time.monotonic(), 0.1))
+        except subprocess.TimeoutExpired:
+            raise self._fail("timed out before exiting") from None
+        if code != 0:
+            raise self._fail(f"exit status {code}")
+
+    def kill(self) -> None:
+        if self.proc.poll() is None:
+            self.proc.kill()
+            try:
+                self.proc.wait(timeout=10)
+            except subprocess.TimeoutExpired:
+                pass
+
+
+def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
+             kinds: Optional[Sequence[str]] = None, *, launches: int = 8,
+             iters: int = 0, bytes: int = 0, passes: int = 0, seed: int = 1,
+             timeout: float = 120.0,
+             spawn: Optional[Callable[[List[str], Dict[str, str]], Any]] = None
+             ) -> Dict[str, Any]:
+    """Run up to two tenants at once on `card`, each a fresh child process
+    under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
+    "fma" | "stream"} and may carry its own "launches"; `kinds`, when given,
+    names the kinds instead. Every child warms up and says READY; only then
+    are all told GO. Returns {"ok": True, "tenants": [the children's
+    cu_tenant_run results]}.
+
+    Each child has `timeout` seconds from its start. The first child that
+    times out, exits non-zero or prints no TENANT line ends the run: the
+    others are killed and {"ok": False, "reason": "child-failed", "detail"}
+    is returned. Nothing is retried."""
+    if not 1 <= len(tenants) <= 2:
+        raise ValueError("run_pair takes one or two tenants")
+    if kinds is not None and len(kinds) != len(tenants):
+        raise ValueError("one kind per tenant")
+    spawn = _spawn if spawn is None else spawn
+    root = str(Path(__file__).resolve().parents[2])
+    children: List[_Child] = []
+    try:
+        for i, tenant in enumerate(tenants):
+            kind = kinds[i] if kinds is not None else tenant["kind"]
+            if kind not in KINDS:
+                raise ValueError(f"unknown tenant kind {kind!r}")
+            env = dict(os.environ)
+            env[ENV_CU_MASK] = mask_hex(int(tenant["mask"]))
+            env["PYTHONPATH"] = os.pathsep.join(
+                [root] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
+            argv = [sys.executable, "-m", CHILD_MODULE, "--child",
+                    "--device", str(card), "--kind", kind,
+                    "--launches", str(int(tenant.get("launches", launches))),
+                    "--iters", str(iters), "--bytes", str(bytes),
+                    "--passes", str(passes), "--seed", str(seed)]
+            try:
+                proc = spawn(argv, env)
+            except OSError as exc:
+                raise _Trouble({"tenant": i, "what": f"not started: {exc}",
+                                "returncode": None}) from None
+            children.append(_Child(i, proc, timeout))
+        results: List[Optional[Dict[str, Any]]] = [None] * len(children)
+        for c in children:
+            c.expect("READY")
+        for c in children:
+            c.go()
+        for c in children:
+            results[c.index] = json.loads(c.expect("TENANT "))
+            c.finish()
+        return {"ok": True, "tenants": results}
+    except _Trouble as trouble:
+        return {"ok": False, "reason": "child-failed", "detail": trouble.args[0]}
+    finally:
+        for c in children:
+            c.kill()
+
+
+def _pattern_checksum(seed: int, nbytes: int) -> int:
+    """XOR of the pattern over a buffer of `nbytes`: the probe's host oracle,
+    which takes at most 2^28 words at a time."""
+    from elastic_gpu_scheduler_amd._native import gpuprobe
+
+    probe = gpuprobe()
+    words, first, x = nbytes // 8, 0, 0
+    while first < words:
+        n = min(words - first, 1 << 28)
+        x ^= probe.pattern_xor(seed, first, n)
+        first += n
+    return x
+
+
+def _balanced(launches: int, seconds: Sequence[float]) -> List[int]:
+    """Launch counts that make both tenants run about equally long. The
+    work of a launch is left as it was measured solo; the tenant whose
+    launches are more than a quarter shorter gets more of them, twice what
+    the solo durations ask for because contention may slow either side, up
+    to the probe's cap. What it runs past the neighbour's end is labelled
+    solo and dropped."""
+    longest = max(seconds)
+    out = []
+    for s in seconds:
+        if s <= 0 or longest / s <= 1.25:
+            out.append(launches)
+        else:
+            out.append(min(MAX_LAUNCHES, math.ceil(2.0 * launches * longest / s) + 1))
+    return out
+
+
+def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
+                     pairs: Sequence[Tuple[str, str]] = ALL_PAIRS,
+                     launches: int = 8, iters: int = 0, bytes: int = 0,
+                     passes: int = 0, seed: int = 1, timeout: float = 120.0,
+                     spawn: Optional[Callable[..., Any]] = None,
+                     expected_checksum: Optional[Callable[[int, int], int]] = None
+                     ) -> Dict[str, Any]:
+    """Each of two tenants' ({"mask": int}) rate alone and next to the other.
+
+    First one solo run per tenant and kind that `pairs` uses, then the pairs
+    in the order given (default fma/fma, stream/stream, fma/stream,
+    stream/fma; the first kind is tenant 0's). Returns {"ok", "solo": [per
+    tenant {kind: {rate, seconds, launches, workgroups}}], "pairs": {"a/b": {"ok",
+    "tenants": [{kind, solo_rate, contended_rate, ratio, contended_launches,
+    launches}]}}}. contended_rate is the median over the launches that lay
+    inside the other tenant's launches (overlap()); with fewer than three of
+    them the tenant gets reason "no-overlap" and no ratio.
+
+    ok says that the measurement is valid (every child exited 0, every
+    stream checksum equals the pattern's, overlap was reached), not that the
+    tenants are isolated: no interference threshold is built in. The first
+    child that fails ends the report ("child-failed"): nothing further is
+    started."""
+    if len(tenants) != 2:
+        raise ValueError("isolation_report takes two tenants")
+    for pair in pairs:
+        if len(pair) != 2 or any(k not in KINDS for k in pair):
+            raise ValueError(f"not a pair of tenant kinds: {pair!r}")
+    expected_checksum = expected_checksum or _pattern_checksum
+    window = {"iters": iters, "bytes": bytes, "passes": passes, "seed": seed,
+              "timeout": timeout, "spawn": spawn}
+    report: Dict[str, Any] = {"ok": True, "solo": [{}, {}], "pairs": {}}
+    checksums: Dict[int, int] = {}
+
+    def flaw(reason: str, **more: Any) -> None:
+        report["ok"] = False
+        report.setdefault("reason", reason)
+        for k, v in more.items():
+            report.setdefault(k, v)
+
+    def sound(result: Mapping[str, Any]) -> Optional[str]:
+        """Why a child's result cannot be used, or None."""
+        if "skipped" in result:
+            return "insufficient-memory"
+        if result["kind"] == "stream":
+            size = int(result["bytes"])
+            if size not in checksums:
+                checksums[size] = expected_checksum(seed, size)
+            if int(result["checksum"]) != checksums[size]:
+                return "bad-checksum"
+        return None
+
+    for i, tenant in enumerate(tenants):
+        for kind in KINDS:
+            if not any(pair[i] == kind for pair in pairs):
+                continue
+            run = run_pair(card, [{"mask": tenant["mask"], "kind": kind}],
+                           launches=launches, **window)
+            if not run["ok"]:
+                flaw(run["reason"], detail=run["detail"])
+                return report
+            result = run["tenants"][0]
+            why = sound(result)
+            if why == "insufficient-memory":
+                flaw(why)
+                return report
+            if why:
+                flaw(why)
+            report["solo"][i][kind] = {
+                "rate": result["rate"],
+                "seconds": statistics.median(l["seconds"] for l in result["launches"]),
+                "launches": len(result["launches"]),
+                "workgroups": result.get("workgroups")}
+
+    for pair in pairs:
+        name = "/".join(pair)
+        counts = _balanced(launches, [report["solo"][i][pair[i]]["seconds"]
+                                      for i in range(2)])
+        run = run_pair(card, [{"mask": tenants[i]["mask"], "kind": pair[i],
+                               "launches": counts[i]} for i in range(2)],
+                       launches=launches, **window)
+        if not run["ok"]:
+            flaw(run["reason"], detail=run["detail"])
+            report["pairs"][name] = {"ok": False, "reason": run["reason"]}
+            return report
+        results = run["tenants"]
+        entry: Dict[str, Any] = {"ok": True, "tenants": []}
+        for i in range(2):
+            why = sound(results[i])
+            if why == "insufficient-memory":
+                flaw(why)
+                report["pairs"][name] = {"ok": False, "reason": why}
+                return report
+            mine, other = results[i]["launches"], results[1 - i]["launches"]
+            labels = [o["label"] for o in overlap(mine, other)]
+            rates = [l["rate"] for l, lab in zip(mine, labels) if lab == "contended"]
+            solo_rate = report["solo"][i][pair[i]]["rate"]
+            t: Dict[str, Any] = {
+                "kind": pair[i], "solo_rate": solo_rate,
+                "contended_launches": len(rates), "launches": len(mine),
+                "solo_launches": labels.count("solo"),
+                "mixed_launches": labels.count("mixed")}
+            if len(rates) < MIN_CONTENDED:
+                why = why or "no-overlap"
+            else:
+                t["contended_rate"] = statistics.median(rates)
+                t["ratio"] = t["contended_rate"] / solo_rate
+            if why:
+                t["reason"] = why
+                entry["ok"] = False
+                entry.setdefault("reason", why)
+                flaw(why)
+            entry["tenants"].append(t)
+        report["pairs"][name] = entry
+    return report
+
+
+if __name__ == "__main__":
+    sys.exit(child_main())

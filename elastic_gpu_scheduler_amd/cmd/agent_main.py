@@ -18,6 +18,8 @@ per-card self-test every Nth cycle and publishes its verdicts as
 --cu-masks enforces gpu-core: every fractional container placed on this node
 is granted a CU mask sized to its share, recorded on the pod as
   elasticgpu.io/cu-mask         per-container {card, mask, cus, shared}
+--co-tenancy qualifies an idle node: per card, two tenants in separate
+processes under disjoint masks, each one's rate alone and next to the other.
 """
 from __future__ import annotations
 
@@ -27,6 +29,18 @@ import logging
 import os
 import sys
 import time
+
+
+def shares_arg(text: str):
+    """"A,B": two gpu-core shares, each 1..100."""
+    try:
+        shares = tuple(int(x) for x in text.split(","))
+    except ValueError:
+        shares = ()
+    if len(shares) != 2 or not all(1 <= s <= 100 for s in shares):
+        raise argparse.ArgumentTypeError(
+            f"expected two shares of 1..100 as A,B, got {text!r}")
+    return shares
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -53,6 +67,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--cu-mask-layout", action="store_true",
                    help="measure how CU-mask bits map to XCDs on each card, "
                         "print it as JSON and exit")
+    p.add_argument("--co-tenancy", nargs="?", type=shares_arg, const=(50, 50),
+                   default=None, metavar="A,B",
+                   help="on each card in turn, run two tenants holding A and B "
+                        "percent (default 50,50) as separate processes under "
+                        "disjoint CU masks and print each one's FMA and HBM "
+                        "stream rate alone and contended as JSON, then exit. "
+                        "For an idle node: it saturates each card for about a "
+                        "second per pair")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -75,6 +97,14 @@ def main(argv=None) -> int:
         agent = NodeAgent(args.node or "local", client=None,
                           prefer_source=args.source)
         print(json.dumps(agent.mask_layouts(), indent=2))
+        return 0
+
+    if args.co_tenancy is not None:
+        agent = NodeAgent(args.node or "local", client=None,
+                          prefer_source=args.source)
+        # One card after another: never more than two children at once.
+        print(json.dumps({card: agent.verify_isolation(card, args.co_tenancy)
+                          for card in sorted(agent.mask_layouts())}, indent=2))
         return 0
 
     if args.dry_run:

@@ -1,0 +1,375 @@
+// Co-tenancy workload: what one tenant of a shared card runs while another
+// process runs next to it.
+//   * cu_tenant_run — a series of back-to-back launches of one fixed piece of
+//     work, either register-resident FP32 FMA chains ("fma") or a read-only
+//     stream over one large allocation ("stream"), each launch stamped with
+//     the device's constant-rate wall clock. The clock is the card's, not the
+//     process's, so two separate processes can lay their launches side by
+//     side afterwards and see which of them really ran at the same time
+//     (agent/cotenancy.py).
+//
+// Same conventions as cumask.hip. Every kernel runs a fixed iteration count,
+// waits on nothing another kernel or process does, and leaves its results
+// through ordinary vector stores or atomics. The stream of a call is created,
+// used and destroyed inside it (RAII), a masked one under the process-wide
+// masked-stream lock.
+#include <hip/hip_runtime.h>
+#include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "common.h"
+
+namespace py = pybind11;
+using gpuprobe::DevBuf;
+using gpuprobe::EventGuard;
+using gpuprobe::MaskWords;
+using gpuprobe::StreamGuard;
+using gpuprobe::pattern_word;
+using gpuprobe::require_device;
+
+namespace {
+
+constexpr int kBlock = 256;       // 4 waves
+constexpr int kGroupsPerCu = 32;  // 8 resident per CU: four fills of the card
+constexpr int kFmaChains = 16;
+constexpr int kStreamUnroll = 4;  // independent 16-byte loads in flight per lane
+constexpr int kMaxLaunches = 64;
+constexpr uint64_t kGiB = 1ULL << 30;
+
+// ---- stamps ----------------------------------------------------------------
+
+// A launch's record is two words, {min start, max end} of wall_clock64(), set
+// to {~0, 0} by the host. One workgroup contributes one pair: its start is read
+// by thread 0 before a barrier that every wave's work comes after, its end
+// after a barrier that every wave reaches with its result store complete.
+// So the record spans the work of every wave of the grid.
+__device__ inline unsigned long long stamp_start() {
+  const unsigned long long t = wall_clock64();
+  __syncthreads();
+  return t;
+}
+
+__device__ inline void stamp_end(unsigned long long* __restrict__ rec,
+                                 unsigned long long t0) {
+  // The lane's result store has left the wave before the barrier is joined.
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const unsigned long long t1 = wall_clock64();
+  if (threadIdx.x == 0) {
+    atomicMin(&rec[0], t0);
+    atomicMax(&rec[1], t1);
+  }
+}
+
+// ---- fma -------------------------------------------------------------------
+
+// kFmaChains independent FMA chains per lane, all in registers; every lane
+// stores its sum once at the end.
+__global__ void __launch_bounds__(kBlock)
+tenant_fma_kernel(float* __restrict__ out, int iters, float a, float b,
+                  unsigned long long* __restrict__ rec) {
+  const unsigned long long t0 = stamp_start();
+  float x[kFmaChains];
+#pragma unroll
+  for (int c = 0; c < kFmaChains; ++c)
+    x[c] = static_cast<float>(threadIdx.x + c) * (1.0f / (kBlock + kFmaChains));
+  for (int i = 0; i < iters; ++i) {
+#pragma unroll
+    for (int c = 0; c < kFmaChains; ++c) x[c] = __builtin_fmaf(x[c], a, b);
+  }
+  float sum = 0.0f;
+#pragma unroll
+  for (int c = 0; c < kFmaChains; ++c) sum += x[c];
+  out[static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x] = sum;
+  stamp_end(rec, t0);
+}
+
+// ---- stream ----------------------------------------------------------------
+
+// buf[i] = {pattern(2i), pattern(2i+1)}, one 16-byte store per element,
+// grid-stride. n16 counts 16-byte elements; all indices are 64-bit.
+__global__ void __launch_bounds__(kBlock)
+tenant_fill_kernel(ulonglong2* __restrict__ buf, uint64_t n16, uint64_t seed) {
+  uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+  for (; i < n16; i += stride) {
+    ulonglong2 v;
+    v.x = pattern_word(seed, 2 * i);
+    v.y = pattern_word(seed, 2 * i + 1);
+    buf[i] = v;
+  }
+}
+
+using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
+
+__device__ inline uint64_t load_fold(const u64x2* p) {
+  const u64x2 v = __builtin_nontemporal_load(p);
+  return v.x ^ v.y;
+}
+
+// Reads the whole buffer `passes` times, grid-stride, kStreamUnroll
+// independent 16-byte non-temporal loads per lane and step, and XOR-folds
+// what it read; the elements past the last whole step are read one at a time.
+// Every index is below n16. `passes` is odd, so each lane's fold over all
+// passes equals its fold over one pass, and the XOR of every lane's word is
+// the XOR of the buffer.
+__global__ void __launch_bounds__(kBlock)
+tenant_stream_kernel(const u64x2* __restrict__ buf, uint64_t n16, int passes,
+                     unsigned long long* __restrict__ out,
+                     unsigned long long* __restrict__ rec) {
+  const unsigned long long t0 = stamp_start();
+  const uint64_t lane = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+  uint64_t fold = 0;
+  for (int p = 0; p < passes; ++p) {
+    uint64_t i = lane;
+    for (; i + (kStreamUnroll - 1) * stride < n16; i += kStreamUnroll * stride) {
+      uint64_t f[kStreamUnroll];
+#pragma unroll
+      for (int u = 0; u < kStreamUnroll; ++u) f[u] = load_fold(buf + i + u * stride);
+#pragma unroll
+      for (int u = 0; u < kStreamUnroll; ++u) fold ^= f[u];
+    }
+    for (; i < n16; i += stride) fold ^= load_fold(buf + i);
+    // Nothing read in one pass may stand in for a load of the next.
+    asm volatile("" ::: "memory");
+  }
+  out[lane] = fold;
+  stamp_end(rec, t0);
+}
+
+// ---- host ------------------------------------------------------------------
+
+enum class Kind { kFma, kStream };
+
+struct Launch {
+  unsigned long long t0 = 0, t1 = 0;
+  double seconds = 0.0, event_seconds = 0.0, rate = 0.0;
+};
+
+struct TenantResult {
+  bool skipped = false;
+  uint64_t free_bytes = 0;
+  Kind kind = Kind::kFma;
+  MaskWords applied;
+  double tick_hz = 0.0;
+  int workgroups = 0;
+  uint64_t bytes = 0;
+  int iters = 0, passes = 0;
+  double work_per_launch = 0.0;  // flops (fma) or bytes (stream)
+  std::vector<Launch> launches;
+  double rate = 0.0;  // median over launches: GFLOP/s or GB/s
+  uint64_t checksum = 0;
+};
+
+TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int launches,
+                        int iters, uint64_t bytes, int passes, uint64_t seed) {
+  require_device(device);
+  const int cus = gpuprobe::device_cus(device);
+  const MaskWords mask =
+      raw_mask.empty() ? MaskWords{} : gpuprobe::fit_mask(raw_mask, cus);
+  launches = std::min(std::max(launches, 1), kMaxLaunches);
+  // The grid depends on the card, never on the mask given here: the same work
+  // either way. (To a process started under ROC_GLOBAL_CU_MASK the runtime
+  // reports only the CUs of that mask as the card's, so there the grid is 32 x
+  // the process's own CUs; every rate is over the work actually launched.)
+  const int grid = kGroupsPerCu * cus;
+  const size_t lanes = static_cast<size_t>(grid) * kBlock;
+
+  TenantResult r;
+  r.kind = kind;
+  r.workgroups = grid;
+  if (kind == Kind::kFma) {
+    if (iters <= 0) iters = 65536;
+    r.iters = std::min(iters, 1 << 18);
+    r.work_per_launch = 2.0 * kFmaChains * static_cast<double>(lanes) * r.iters;
+  } else {
+    if (bytes == 0) bytes = kGiB;
+    bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, 16), 16 * kGiB);
+    r.bytes = bytes & ~static_cast<uint64_t>(15);
+    if (passes <= 0) passes = 127;
+    passes = std::min(passes, 4095);
+    r.passes = passes | 1;  // odd: the XOR over all passes is that of one
+    r.work_per_launch = static_cast<double>(r.bytes) * r.passes;
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    r.free_bytes = free_b;
+    if (free_b < r.bytes + kGiB) {
+      r.skipped = true;
+      return r;
+    }
+  }
+  int clock_khz = 0;
+  HIP_CHECK(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, device));
+  if (clock_khz <= 0)
+    throw std::runtime_error("cu_tenant_run: device reports no wall-clock rate");
+  r.tick_hz = static_cast<double>(clock_khz) * 1e3;
+
+  const uint64_t n16 = r.bytes / 16;
+  DevBuf buf, out, recs;
+  if (kind == Kind::kStream) buf.alloc(r.bytes);
+  out.alloc(lanes * (kind == Kind::kFma ? sizeof(float) : sizeof(unsigned long long)));
+  // One record per timed launch, and one more for the warm-up.
+  std::vector<unsigned long long> h_recs(2 * static_cast<size_t>(launches + 1));
+  for (size_t i = 0; i < h_recs.size(); i += 2) {
+    h_recs[i] = ~0ULL;
+    h_recs[i + 1] = 0;
+  }
+  recs.alloc(h_recs.size() * sizeof(unsigned long long));
+  HIP_CHECK(hipMemcpy(recs.p, h_recs.data(), h_recs.size() * sizeof(unsigned long long),
+                      hipMemcpyHostToDevice));
+  HIP_CHECK(hipDeviceSynchronize());
+  std::vector<EventGuard> ev(2 * static_cast<size_t>(launches));
+  for (auto& e : ev) e.create();
+
+  std::vector<unsigned long long> h_out;
+  {
+    StreamGuard g;
+    gpuprobe::open_stream(g, mask, r.applied);
+    auto launch = [&](int slot) {
+      unsigned long long* rec = recs.as<unsigned long long>() + 2 * slot;
+      if (kind == Kind::kFma)
+        hipLaunchKernelGGL(tenant_fma_kernel, dim3(grid), dim3(kBlock), 0, g.s,
+                           out.as<float>(), r.iters, 0.999f, 0.001f, rec);
+      else
+        hipLaunchKernelGGL(tenant_stream_kernel, dim3(grid), dim3(kBlock), 0, g.s,
+                           buf.as<const u64x2>(), n16, r.passes,
+                           out.as<unsigned long long>(), rec);
+      HIP_CHECK(hipGetLastError());
+    };
+    if (kind == Kind::kStream) {
+      hipLaunchKernelGGL(tenant_fill_kernel, dim3(grid), dim3(kBlock), 0, g.s,
+                         buf.as<ulonglong2>(), n16, seed);
+      HIP_CHECK(hipGetLastError());
+    }
+    // Warm-up, not timed: the same launch once, so that the code object is
+    // loaded and the clocks have settled under this load before the timed ones.
+    launch(launches);
+    for (int l = 0; l < launches; ++l) {
+      HIP_CHECK(hipEventRecord(ev[2 * l].e, g.s));
+      launch(l);
+      HIP_CHECK(hipEventRecord(ev[2 * l + 1].e, g.s));
+    }
+    HIP_CHECK(hipStreamSynchronize(g.s));
+    HIP_CHECK(hipMemcpy(h_recs.data(), recs.p, h_recs.size() * sizeof(unsigned long long),
+                        hipMemcpyDeviceToHost));
+    if (kind == Kind::kStream) {
+      h_out.resize(lanes);
+      HIP_CHECK(hipMemcpy(h_out.data(), out.p, lanes * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost));
+    }
+  }  // the stream is gone before the result is looked at
+
+  for (unsigned long long w : h_out) r.checksum ^= w;  // of the last launch
+  std::vector<double> rates;
+  for (int l = 0; l < launches; ++l) {
+    Launch e;
+    e.t0 = h_recs[2 * l];
+    e.t1 = h_recs[2 * l + 1];
+    if (e.t0 == ~0ULL || e.t1 <= e.t0)
+      throw std::runtime_error("cu_tenant_run: launch " + std::to_string(l) +
+                               " left no usable clock record");
+    e.seconds = static_cast<double>(e.t1 - e.t0) / r.tick_hz;
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * l].e, ev[2 * l + 1].e));
+    e.event_seconds = static_cast<double>(ms) * 1e-3;
+    e.rate = r.work_per_launch / e.seconds / 1e9;
+    rates.push_back(e.rate);
+    r.launches.push_back(e);
+  }
+  std::sort(rates.begin(), rates.end());
+  const size_t n = rates.size();
+  r.rate = n % 2 ? rates[n / 2] : 0.5 * (rates[n / 2 - 1] + rates[n / 2]);
+  return r;
+}
+
+}  // namespace
+
+void register_cotenant(py::module_& m) {
+  m.def(
+      "cu_tenant_run",
+      [](int device, py::object mask, const std::string& kind, int launches, int iters,
+         uint64_t bytes, int passes, uint64_t seed) {
+        const MaskWords words = gpuprobe::mask_from_python(mask);
+        Kind k;
+        if (kind == "fma")
+          k = Kind::kFma;
+        else if (kind == "stream")
+          k = Kind::kStream;
+        else
+          throw py::value_error("cu_tenant_run: kind must be \"fma\" or \"stream\"");
+        TenantResult r;
+        {
+          py::gil_scoped_release release;
+          r = run_tenant(device, words, k, launches, iters, bytes, passes, seed);
+        }
+        py::dict d;
+        if (r.skipped) {
+          d["skipped"] = "insufficient free memory";
+          d["bytes"] = r.bytes;
+          d["free_bytes"] = r.free_bytes;
+          return d;
+        }
+        d["kind"] = kind;
+        d["applied_mask"] = gpuprobe::mask_to_python(r.applied);
+        d["tick_hz"] = r.tick_hz;
+        d["workgroups"] = r.workgroups;
+        if (k == Kind::kFma) {
+          d["iters"] = r.iters;
+        } else {
+          d["bytes"] = r.bytes;
+          d["passes"] = r.passes;
+          d["checksum"] = r.checksum;
+        }
+        d["work_per_launch"] = r.work_per_launch;
+        py::list launches_out;
+        for (const auto& e : r.launches) {
+          py::dict l;
+          l["t0"] = e.t0;
+          l["t1"] = e.t1;
+          l["seconds"] = e.seconds;
+          l["event_seconds"] = e.event_seconds;
+          l["rate"] = e.rate;
+          launches_out.append(l);
+        }
+        d["launches"] = launches_out;
+        d["rate"] = r.rate;
+        return d;
+      },
+      py::arg("device") = 0, py::arg("mask") = py::none(), py::arg("kind") = "fma",
+      py::arg("launches") = 8, py::arg("iters") = 0, py::arg("bytes") = 0,
+      py::arg("passes") = 0, py::arg("seed") = 1,
+      "One tenant's workload, stamped with the card's wall clock. `mask` as in "
+      "cu_occupancy (None: a plain stream, which is what a process started "
+      "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\" or \"stream\", anything "
+      "else raises ValueError before the device is touched. After one untimed "
+      "launch, `launches` (1..64) launches of the same work run back to back "
+      "on one stream, each between its own pair of events; the grid is 32 x "
+      "CUs workgroups of 256 lanes whatever `mask` is, CUs being what the "
+      "device reports to this process.\n\n"
+      "fma: 16 independent FP32 FMA chains of `iters` (default 65536, at most "
+      "262144) per lane, in registers. stream: every lane reads one allocation "
+      "of `bytes` (default 1 GiB, rounded down to a multiple of 16, clamped to "
+      "16 B .. 16 GiB) `passes` times (default 127, at most 4095, an even value "
+      "is raised by one) with 16-byte non-temporal loads, four in flight, and "
+      "XOR-folds them; the buffer holds pattern_word(`seed`, w), written once "
+      "on the same stream before anything is timed. When less than bytes + 1 "
+      "GiB is free nothing is allocated and {skipped, bytes, free_bytes} is "
+      "returned. A buffer that fits the Infinity Cache (256 MiB) measures the "
+      "cache, not HBM.\n\n"
+      "Every launch records {earliest start, latest end} of wall_clock64() over "
+      "all its workgroups; the clock runs at `tick_hz` "
+      "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
+      "{kind, applied_mask, tick_hz, workgroups, iters | bytes, passes, checksum, "
+      "work_per_launch: flops or bytes, launches: [{t0, t1, seconds: (t1 - t0) "
+      "/ tick_hz, event_seconds, rate}], rate}; rates are GFLOP/s or GB/s over "
+      "`seconds`, the top-level one the median over launches. checksum (stream "
+      "only) is the XOR of the words the last launch's lanes stored and equals "
+      "pattern_xor(seed, 0, bytes // 8) when every byte was read.");
+}

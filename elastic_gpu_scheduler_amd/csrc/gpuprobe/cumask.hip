@@ -28,7 +28,20 @@
 #include "common.h"
 
 namespace py = pybind11;
+using gpuprobe::DevBuf;
+using gpuprobe::EventGuard;
+using gpuprobe::MaskWords;
+using gpuprobe::StreamGuard;
+using gpuprobe::device_cus;
+using gpuprobe::fit_mask;
+using gpuprobe::mask_from_python;
+using gpuprobe::mask_to_python;
+using gpuprobe::open_stream;
 using gpuprobe::require_device;
+
+// ---- shared with cotenant.hip (declared in common.h) -------------------------
+
+namespace gpuprobe {
 
 namespace {
 
@@ -37,47 +50,7 @@ namespace {
 constexpr int kMaxCus = 256;
 constexpr int kMaxMaskWords = kMaxCus / 32;
 
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  void alloc(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes)); }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-struct StreamGuard {
-  hipStream_t s = nullptr;
-  // Released after the destructor body, that is after the stream is gone.
-  std::unique_lock<std::mutex> masked;
-  StreamGuard() = default;
-  StreamGuard(const StreamGuard&) = delete;
-  StreamGuard& operator=(const StreamGuard&) = delete;
-  ~StreamGuard() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-
-struct EventGuard {
-  hipEvent_t e = nullptr;
-  EventGuard() = default;
-  EventGuard(const EventGuard&) = delete;
-  EventGuard& operator=(const EventGuard&) = delete;
-  ~EventGuard() {
-    if (e) (void)hipEventDestroy(e);
-  }
-  void create() { HIP_CHECK(hipEventCreate(&e)); }
-};
-
-// A mask as the HIP API takes it: word w bit b is CU 32 * w + b. Empty means
-// "no mask" (a plain stream).
-using MaskWords = std::vector<uint32_t>;
+}  // namespace
 
 int device_cus(int device) {
   int cus = 0;
@@ -88,7 +61,6 @@ int device_cus(int device) {
   return cus;
 }
 
-// Sizes `mask` to ceil(cus / 32) words; a bit at or above `cus` is an error.
 MaskWords fit_mask(const MaskWords& mask, int cus) {
   const size_t n_words = static_cast<size_t>((cus + 31) / 32);
   MaskWords out(n_words, 0u);
@@ -107,12 +79,14 @@ MaskWords fit_mask(const MaskWords& mask, int cus) {
   return out;
 }
 
+namespace {
+
 // Held for as long as a masked stream exists: the entry points release the
 // GIL, and two threads must not each hold one.
 std::mutex g_masked_stream;
 
-// Creates the stream of one probe call: masked when `mask` is non-empty.
-// `applied` receives what the runtime reads back for a masked stream.
+}  // namespace
+
 void open_stream(StreamGuard& g, const MaskWords& mask, MaskWords& applied) {
   applied.clear();
   if (mask.empty()) {
@@ -126,6 +100,34 @@ void open_stream(StreamGuard& g, const MaskWords& mask, MaskWords& applied) {
   HIP_CHECK(hipExtStreamGetCUMask(g.s, static_cast<uint32_t>(applied.size()),
                                   applied.data()));
 }
+
+// None -> empty. Otherwise a positive int with no bit at or above kMaxCus,
+// checked here, before any HIP call; the device's own CU count is checked in
+// fit_mask before anything is created or launched.
+MaskWords mask_from_python(const py::object& mask) {
+  if (mask.is_none()) return {};
+  if (!py::isinstance<py::int_>(mask)) throw py::type_error("mask must be an int or None");
+  if (mask.attr("__le__")(0).cast<bool>())
+    throw py::value_error("cu mask must be positive");
+  if (mask.attr("bit_length")().cast<int>() > kMaxCus)
+    throw py::value_error("cu mask has a bit at or above CU " + std::to_string(kMaxCus));
+  MaskWords words(kMaxMaskWords, 0u);
+  for (int w = 0; w < kMaxMaskWords; ++w)
+    words[w] = mask.attr("__rshift__")(32 * w).attr("__and__")(0xFFFFFFFFu).cast<uint32_t>();
+  return words;
+}
+
+py::object mask_to_python(const MaskWords& words) {
+  if (words.empty()) return py::none();
+  py::object v = py::int_(0);
+  for (size_t w = words.size(); w-- > 0;)
+    v = v.attr("__lshift__")(32).attr("__or__")(py::int_(words[w]));
+  return v;
+}
+
+}  // namespace gpuprobe
+
+namespace {
 
 // ---- occupancy -------------------------------------------------------------
 
@@ -337,32 +339,6 @@ Throughput run_throughput(int device, const MaskWords& raw_mask, int iters) {
   const double flops = 2.0 * kFmaChains * static_cast<double>(n) * iters;
   r.gflops = r.seconds > 0 ? flops / r.seconds / 1e9 : 0.0;
   return r;
-}
-
-// ---- Python <-> mask -------------------------------------------------------
-
-// None -> empty. Otherwise a positive int with no bit at or above kMaxCus,
-// checked here, before any HIP call; the device's own CU count is checked in
-// fit_mask before anything is created or launched.
-MaskWords mask_from_python(const py::object& mask) {
-  if (mask.is_none()) return {};
-  if (!py::isinstance<py::int_>(mask)) throw py::type_error("mask must be an int or None");
-  if (mask.attr("__le__")(0).cast<bool>())
-    throw py::value_error("cu mask must be positive");
-  if (mask.attr("bit_length")().cast<int>() > kMaxCus)
-    throw py::value_error("cu mask has a bit at or above CU " + std::to_string(kMaxCus));
-  MaskWords words(kMaxMaskWords, 0u);
-  for (int w = 0; w < kMaxMaskWords; ++w)
-    words[w] = mask.attr("__rshift__")(32 * w).attr("__and__")(0xFFFFFFFFu).cast<uint32_t>();
-  return words;
-}
-
-py::object mask_to_python(const MaskWords& words) {
-  if (words.empty()) return py::none();
-  py::object v = py::int_(0);
-  for (size_t w = words.size(); w-- > 0;)
-    v = v.attr("__lshift__")(32).attr("__or__")(py::int_(words[w]));
-  return v;
 }
 
 py::tuple key_tuple(const CuKey& k) { return py::make_tuple(k[0], k[1], k[2], k[3]); }

@@ -13,8 +13,8 @@
 //     verifies it, proving a bound pod's container really landed on the card
 //     indexes the scheduler chose (placement verification).
 // The deep card self-test (HBM pattern, per-XCD bandwidth, MFMA check) lives
-// in selftest.hip, the CU-mask probes in cumask.hip; both register into this
-// module.
+// in selftest.hip, the CU-mask probes in cumask.hip, the co-tenancy workload
+// in cotenant.hip; all three register into this module.
 //
 // All entry points are bounded in memory and time; kernels are trivial
 // streaming loops sized with grid-stride so any buffer size fills the chip
@@ -275,4 +275,5 @@ PYBIND11_MODULE(_gpuprobe, m) {
         py::arg("mib") = 16, py::call_guard<py::gil_scoped_release>());
   register_selftest(m);
   register_cumask(m);
+  register_cotenant(m);
 }

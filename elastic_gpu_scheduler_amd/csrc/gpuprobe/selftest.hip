@@ -26,20 +26,11 @@
 #include "common.h"
 
 namespace py = pybind11;
+using gpuprobe::DevBuf;
+using gpuprobe::pattern_word;  // the test pattern: common.h
 using gpuprobe::require_device;
 
 namespace {
-
-// ---- the test pattern (single definition, host and device) ---------------
-
-// splitmix64 finaliser of (seed, word index). `w` indexes the buffer viewed
-// as 8-byte words.
-__host__ __device__ inline uint64_t pattern_word(uint64_t seed, uint64_t w) {
-  uint64_t z = seed + (w + 1) * 0x9E3779B97F4A7C15ULL;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
-}
 
 constexpr uint64_t kMaxXorWords = 1ULL << 28;  // 2 GiB of pattern
 constexpr uint64_t kXcdSeed = 0x5EEDC0DE0BADF00DULL;
@@ -52,23 +43,6 @@ uint64_t pattern_xor(uint64_t seed, uint64_t first_word, uint64_t n_words) {
   for (uint64_t i = 0; i < n_words; ++i) x ^= pattern_word(seed, first_word + i);
   return x;
 }
-
-// ---- small RAII so an exception mid-test frees the card's memory ---------
-
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  void alloc(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes)); }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
 
 constexpr int kBlock = 256;  // 4 waves
 
