@@ -28,14 +28,16 @@ equivalent's control logic:
     disjoint physical CUs;
   * verify_isolation() — a qualification run for an idle card: two tenants
     in separate processes under disjoint masks, each one's rate alone and
-    next to the other (agent/cotenancy.py).
+    next to the other (agent/cotenancy.py);
+  * cache_profile() — likewise for an idle card: one tenant alone, its
+    re-read rate by working-set size, which shows where the caches end.
 """
 from __future__ import annotations
 
 import json
 import logging
 import time
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Sequence
 
 from elastic_gpu_scheduler_amd.agent import inventory as inv
 from elastic_gpu_scheduler_amd.agent import topology as topo
@@ -57,6 +59,10 @@ HBM_HEALTH_THRESHOLD_GBPS = 1000.0
 # Seed of the deep self-test's HBM pattern (any value serves; fixed so a
 # reported word index and XOR can be reproduced).
 SELF_TEST_PATTERN_SEED = 0x6A09E667F3BCC908
+
+# Working sets of cache_profile(): below, around and above the aggregate L2
+# (32 MiB) and the Infinity Cache (256 MiB).
+CACHE_PROFILE_SIZES = tuple(m << 20 for m in (2, 8, 16, 24, 48, 128, 192, 512, 1024))
 
 
 class NodeAgent:
@@ -425,8 +431,14 @@ class NodeAgent:
         processes under the masks the planner would grant them, exactly as
         containers are wired: each tenant's FMA and HBM-stream rate alone and
         while the other runs (cotenancy.isolation_report, to which `window`
-        is passed: pairs, launches, iters, bytes, passes, timeout). Returns
-        that report plus "tenants": [{core, mask, cus}].
+        is passed: pairs, launches, iters, bytes, passes, timeout, windows).
+        Returns that report plus "tenants": [{core, mask, cus}].
+
+        pairs=cotenancy.CACHE_PAIRS brings in the third kind, a tenant that
+        re-reads a working set small enough for a cache; `windows` gives a
+        kind its own iters / bytes / passes, e.g. {"cache": {"bytes": 12 <<
+        20, "passes": cotenancy.cache_passes(12 << 20)}} next to the default
+        1 GiB streamer.
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched
@@ -459,6 +471,37 @@ class NodeAgent:
         report = cotenancy.isolation_report(
             card, [{"mask": g.mask} for g in grants], **window)
         report["tenants"] = tenants
+        return report
+
+    def cache_profile(self, card: int, share: int = 50,
+                      sizes: Sequence[int] = CACHE_PROFILE_SIZES,
+                      **window: Any) -> Dict[str, Any]:
+        """One tenant holding `share` percent of `card`, alone, re-reading
+        working sets of `sizes` bytes (default 2 MiB .. 1 GiB), one process
+        per size under the mask the planner would grant it: where the rate
+        steps down, the working set has left a cache (cotenancy.
+        cache_profile, to which `window` is passed: launches, passes,
+        timeout). Returns that report plus "tenant": {core, mask, cus}.
+
+        Gated as verify_isolation is: a scratch plan over the measured
+        layout, and nothing is launched when the layout is unknown or not
+        interleaved or the mask is not whole granules
+        ("unsupported-layout"). For an idle card."""
+        from elastic_gpu_scheduler_amd.agent import cotenancy
+
+        layout = self.mask_layouts().get(card)
+        if not layout or not layout.get("interleaved"):
+            return {"ok": False, "reason": "unsupported-layout"}
+        try:
+            plan = CardMaskPlan(int(layout["cus"]), int(layout["granule"]))
+        except ValueError:
+            return {"ok": False, "reason": "unsupported-layout"}
+        grant = plan.allocate(0, int(share))
+        if not plan.whole_granules(grant.mask):
+            return {"ok": False, "reason": "unsupported-layout"}
+        report = cotenancy.cache_profile(card, grant.mask, list(sizes), **window)
+        report["tenant"] = {"core": int(share), "mask": mask_hex(grant.mask),
+                            "cus": grant.cus}
         return report
 
 

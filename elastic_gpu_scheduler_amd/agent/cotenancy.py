@@ -10,7 +10,13 @@ those that provably ran while the other tenant was running:
 
   * overlap()          — per launch of A, the fraction covered by B's launches;
   * run_pair()         — up to two children at once, READY / GO handshake;
-  * isolation_report() — solo rates first, then the pairs, then the ratios.
+  * isolation_report() — solo rates first, then the pairs, then the ratios;
+  * cache_profile()    — one tenant alone, its rate by working-set size.
+
+A tenant is one of three kinds: "fma" (registers only), "stream" (1 GiB read
+through, non-temporal) or "cache" (a working set re-read with plain loads,
+every byte of it live for the whole launch). Each kind may be given a window
+of its own, so a 12 MiB cache tenant can sit next to a 1 GiB streamer.
 
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
@@ -35,9 +41,16 @@ from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 from elastic_gpu_scheduler_amd.agent.cumask import mask_hex
 from elastic_gpu_scheduler_amd.agent.wiring import ENV_CU_MASK
 
-KINDS = ("fma", "stream")
+KINDS = ("fma", "stream", "cache")
 ALL_PAIRS: Tuple[Tuple[str, str], ...] = (
     ("fma", "fma"), ("stream", "stream"), ("fma", "stream"), ("stream", "fma"))
+# The pairs that say what a neighbour does to a tenant living in a cache.
+CACHE_PAIRS: Tuple[Tuple[str, str], ...] = (
+    ("cache", "cache"), ("cache", "stream"), ("stream", "cache"), ("cache", "fma"))
+# What may differ from tenant to tenant, or from kind to kind, within one call.
+WINDOW_KEYS = ("iters", "bytes", "passes")
+# Kinds whose result carries a checksum of the buffer they read.
+READING_KINDS = ("stream", "cache")
 
 # A launch counts as contended when at least this much of it lies inside the
 # other tenant's launches: the few microseconds between two back-to-back
@@ -46,6 +59,13 @@ CONTENDED_FRACTION = 0.95
 # Never compute a ratio from fewer contended launches than this.
 MIN_CONTENDED = 3
 MAX_LAUNCHES = 64  # the probe's own cap
+MAX_CACHE_PASSES = 65535  # the probe's own cap for the cache kind
+# What a default stream launch reads (1 GiB x 127 passes). A cache launch that
+# reads as much lasts about as long as a stream or fma launch beside it, so
+# the balanced launch counts stay below MAX_LAUNCHES.
+PAIR_LAUNCH_BYTES = 127 << 30
+# What a launch of the working-set sweep reads: a few milliseconds at any size.
+PROFILE_LAUNCH_BYTES = 16 << 30
 CHILD_MODULE = "elastic_gpu_scheduler_amd.agent.cotenancy"
 
 Launches = Sequence[Mapping[str, Any]]
@@ -85,6 +105,12 @@ def overlap(launches_a: Launches, launches_b: Launches) -> List[Dict[str, Any]]:
                  else "solo" if covered == 0 else "mixed")
         out.append({"fraction": fraction, "label": label})
     return out
+
+
+def cache_passes(nbytes: int, launch_bytes: int = PAIR_LAUNCH_BYTES) -> int:
+    """The odd number of passes with which a cache tenant of `nbytes` reads
+    about `launch_bytes` per launch, within the probe's 1..65535."""
+    return min(MAX_CACHE_PASSES, max(1, launch_bytes // max(int(nbytes), 16))) | 1
 
 
 # --- child ------------------------------------------------------------------
@@ -210,7 +236,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
              ) -> Dict[str, Any]:
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
-    "fma" | "stream"} and may carry its own "launches"; `kinds`, when given,
+    "fma" | "stream" | "cache"} and may carry its own "launches", "iters",
+    "bytes" and "passes" in place of the call-wide ones; `kinds`, when given,
     names the kinds instead. Every child warms up and says READY; only then
     are all told GO. Returns {"ok": True, "tenants": [the children's
     cu_tenant_run results]}.
@@ -238,8 +265,10 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
             argv = [sys.executable, "-m", CHILD_MODULE, "--child",
                     "--device", str(card), "--kind", kind,
                     "--launches", str(int(tenant.get("launches", launches))),
-                    "--iters", str(iters), "--bytes", str(bytes),
-                    "--passes", str(passes), "--seed", str(seed)]
+                    "--iters", str(tenant.get("iters", iters)),
+                    "--bytes", str(tenant.get("bytes", bytes)),
+                    "--passes", str(tenant.get("passes", passes)),
+                    "--seed", str(seed)]
             try:
                 proc = spawn(argv, env)
             except OSError as exc:
@@ -298,7 +327,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                      launches: int = 8, iters: int = 0, bytes: int = 0,
                      passes: int = 0, seed: int = 1, timeout: float = 120.0,
                      spawn: Optional[Callable[..., Any]] = None,
-                     expected_checksum: Optional[Callable[[int, int], int]] = None
+                     expected_checksum: Optional[Callable[[int, int], int]] = None,
+                     windows: Optional[Mapping[str, Mapping[str, int]]] = None
                      ) -> Dict[str, Any]:
     """Each of two tenants' ({"mask": int}) rate alone and next to the other.
 
@@ -311,8 +341,17 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     inside the other tenant's launches (overlap()); with fewer than three of
     them the tenant gets reason "no-overlap" and no ratio.
 
+    `windows` gives a kind its own iters / bytes / passes in place of the
+    call-wide ones, in the solo runs and in the pairs alike, for example
+    {"cache": {"bytes": 12 << 20, "passes": cache_passes(12 << 20)},
+    "stream": {"bytes": 1 << 30}}: a small cache tenant next to a large
+    streamer. A cache launch at the probe's default passes lasts about a
+    millisecond, a default stream launch over twenty: give the cache kind
+    cache_passes(bytes), or the launch count it would need to keep up is cut
+    at 64 and the neighbour's launches past its end are dropped as solo.
+
     ok says that the measurement is valid (every child exited 0, every
-    stream checksum equals the pattern's, overlap was reached), not that the
+    stream and cache checksum equals the pattern's, overlap was reached), not that the
     tenants are isolated: no interference threshold is built in. The first
     child that fails ends the report ("child-failed"): nothing further is
     started."""
@@ -321,6 +360,10 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     for pair in pairs:
         if len(pair) != 2 or any(k not in KINDS for k in pair):
             raise ValueError(f"not a pair of tenant kinds: {pair!r}")
+    windows = {kind: dict(w) for kind, w in (windows or {}).items()}
+    for kind, w in windows.items():
+        if kind not in KINDS or any(k not in WINDOW_KEYS for k in w):
+            raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
     expected_checksum = expected_checksum or _pattern_checksum
     window = {"iters": iters, "bytes": bytes, "passes": passes, "seed": seed,
               "timeout": timeout, "spawn": spawn}
@@ -337,7 +380,7 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         """Why a child's result cannot be used, or None."""
         if "skipped" in result:
             return "insufficient-memory"
-        if result["kind"] == "stream":
+        if result["kind"] in READING_KINDS:
             size = int(result["bytes"])
             if size not in checksums:
                 checksums[size] = expected_checksum(seed, size)
@@ -349,7 +392,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         for kind in KINDS:
             if not any(pair[i] == kind for pair in pairs):
                 continue
-            run = run_pair(card, [{"mask": tenant["mask"], "kind": kind}],
+            run = run_pair(card, [{"mask": tenant["mask"], "kind": kind,
+                                   **windows.get(kind, {})}],
                            launches=launches, **window)
             if not run["ok"]:
                 flaw(run["reason"], detail=run["detail"])
@@ -372,7 +416,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         counts = _balanced(launches, [report["solo"][i][pair[i]]["seconds"]
                                       for i in range(2)])
         run = run_pair(card, [{"mask": tenants[i]["mask"], "kind": pair[i],
-                               "launches": counts[i]} for i in range(2)],
+                               "launches": counts[i], **windows.get(pair[i], {})}
+                              for i in range(2)],
                        launches=launches, **window)
         if not run["ok"]:
             flaw(run["reason"], detail=run["detail"])
@@ -408,6 +453,48 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
             entry["tenants"].append(t)
         report["pairs"][name] = entry
     return report
+
+
+def cache_profile(card: int, mask: int, sizes: Sequence[int], *,
+                  launches: int = 8, passes: int = 0, seed: int = 1,
+                  timeout: float = 120.0,
+                  spawn: Optional[Callable[..., Any]] = None,
+                  expected_checksum: Optional[Callable[[int, int], int]] = None
+                  ) -> Dict[str, Any]:
+    """One cache tenant alone under `mask`, once per working-set size: where
+    the rate steps down is where the working set stops fitting a cache. One
+    child per size, in the order given, never two at once. `passes` 0 reads
+    about 16 GiB per launch at every size (cache_passes). Returns {"ok",
+    "profile": [{bytes, bytes_per_cu, rate, seconds, passes}]}, rate in GB/s
+    and seconds the median over the launches.
+
+    The first child that fails ends the sweep ("child-failed"), as does one
+    that finds too little free memory; a wrong checksum makes it not ok but
+    the figures are kept. Nothing is retried."""
+    expected_checksum = expected_checksum or _pattern_checksum
+    out: Dict[str, Any] = {"ok": True, "profile": []}
+    for size in sizes:
+        size = int(size)
+        run = run_pair(card, [{
+            "mask": mask, "kind": "cache", "bytes": size,
+            "passes": passes or cache_passes(size, PROFILE_LAUNCH_BYTES)}],
+            launches=launches, seed=seed, timeout=timeout, spawn=spawn)
+        if not run["ok"]:
+            out.update(ok=False, reason=run["reason"], detail=run["detail"])
+            return out
+        result = run["tenants"][0]
+        if "skipped" in result:
+            out.update(ok=False, reason="insufficient-memory")
+            return out
+        if int(result["checksum"]) != expected_checksum(seed, int(result["bytes"])):
+            out["ok"] = False
+            out.setdefault("reason", "bad-checksum")
+        out["profile"].append({
+            "bytes": result["bytes"], "bytes_per_cu": result.get("bytes_per_cu"),
+            "rate": result["rate"],
+            "seconds": statistics.median(l["seconds"] for l in result["launches"]),
+            "passes": result["passes"]})
+    return out
 
 
 if __name__ == "__main__":

@@ -20,6 +20,7 @@ is granted a CU mask sized to its share, recorded on the pod as
   elasticgpu.io/cu-mask         per-container {card, mask, cus, shared}
 --co-tenancy qualifies an idle node: per card, two tenants in separate
 processes under disjoint masks, each one's rate alone and next to the other.
+--co-tenancy-cache does the same for a tenant whose working set fits a cache.
 """
 from __future__ import annotations
 
@@ -41,6 +42,18 @@ def shares_arg(text: str):
         raise argparse.ArgumentTypeError(
             f"expected two shares of 1..100 as A,B, got {text!r}")
     return shares
+
+
+def mib_list_arg(text: str):
+    """"M[,M...]": working-set sizes in MiB, each 1..1024."""
+    try:
+        sizes = tuple(int(x) for x in text.split(","))
+    except ValueError:
+        sizes = ()
+    if not sizes or not all(1 <= m <= 1024 for m in sizes):
+        raise argparse.ArgumentTypeError(
+            f"expected sizes of 1..1024 MiB as M[,M...], got {text!r}")
+    return sizes
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -75,6 +88,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "stream rate alone and contended as JSON, then exit. "
                         "For an idle node: it saturates each card for about a "
                         "second per pair")
+    p.add_argument("--co-tenancy-cache", nargs="?", type=mib_list_arg,
+                   const=(12, 128), default=None, metavar="MIB[,MIB...]",
+                   help="with --co-tenancy: instead of the FMA and stream "
+                        "pairs, run a tenant that re-reads a working set of "
+                        "each size (default 12,128 MiB) next to another such "
+                        "tenant, next to the 1 GiB streamer (both ways round) "
+                        "and next to an FMA tenant, and print one report per "
+                        "card and size")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -97,6 +118,27 @@ def main(argv=None) -> int:
         agent = NodeAgent(args.node or "local", client=None,
                           prefer_source=args.source)
         print(json.dumps(agent.mask_layouts(), indent=2))
+        return 0
+
+    if args.co_tenancy_cache is not None and args.co_tenancy is None:
+        print("--co-tenancy-cache needs --co-tenancy", file=sys.stderr)
+        return 2
+
+    if args.co_tenancy_cache is not None:
+        from elastic_gpu_scheduler_amd.agent.cotenancy import (CACHE_PAIRS,
+                                                               cache_passes)
+
+        agent = NodeAgent(args.node or "local", client=None,
+                          prefer_source=args.source)
+        # One card and one size after another: never more than two children
+        # at once. A cache launch is given the bytes of a default stream
+        # launch, so that neither tenant of a pair outlasts the other by far.
+        print(json.dumps({card: {str(mib): agent.verify_isolation(
+            card, args.co_tenancy, pairs=CACHE_PAIRS,
+            windows={"cache": {"bytes": mib << 20,
+                               "passes": cache_passes(mib << 20)}})
+            for mib in args.co_tenancy_cache}
+            for card in sorted(agent.mask_layouts())}, indent=2))
         return 0
 
     if args.co_tenancy is not None:

@@ -1,9 +1,11 @@
 // Co-tenancy workload: what one tenant of a shared card runs while another
 // process runs next to it.
 //   * cu_tenant_run — a series of back-to-back launches of one fixed piece of
-//     work, either register-resident FP32 FMA chains ("fma") or a read-only
-//     stream over one large allocation ("stream"), each launch stamped with
-//     the device's constant-rate wall clock. The clock is the card's, not the
+//     work, either register-resident FP32 FMA chains ("fma"), a read-only
+//     stream over one large allocation ("stream") or repeated reads of a
+//     working set that every workgroup keeps to itself ("cache"), each launch
+//     stamped with the device's constant-rate wall clock. The clock is the
+//     card's, not the
 //     process's, so two separate processes can lay their launches side by
 //     side afterwards and see which of them really ran at the same time
 //     (agent/cotenancy.py).
@@ -37,10 +39,12 @@ namespace {
 
 constexpr int kBlock = 256;       // 4 waves
 constexpr int kGroupsPerCu = 32;  // 8 resident per CU: four fills of the card
+constexpr int kCacheGroupsPerCu = 8;  // "cache": one fill, every chunk live at once
 constexpr int kFmaChains = 16;
 constexpr int kStreamUnroll = 4;  // independent 16-byte loads in flight per lane
 constexpr int kMaxLaunches = 64;
 constexpr uint64_t kGiB = 1ULL << 30;
+constexpr uint64_t kMiB = 1ULL << 20;
 
 // ---- stamps ----------------------------------------------------------------
 
@@ -144,9 +148,50 @@ tenant_stream_kernel(const u64x2* __restrict__ buf, uint64_t n16, int passes,
   stamp_end(rec, t0);
 }
 
+// ---- cache -----------------------------------------------------------------
+
+__device__ inline uint64_t load_fold_cached(const u64x2* p) {
+  const u64x2 v = *p;  // default cache policy: the line stays in L1, L2 and beyond
+  return v.x ^ v.y;
+}
+
+// Workgroup b reads its own elements [b * n16 / grid, (b + 1) * n16 / grid)
+// `passes` times with plain 16-byte loads, kStreamUnroll independent ones per
+// lane and step, the elements past the last whole step one at a time, and
+// XOR-folds what it read. The grid is one resident fill of the card, so every
+// chunk is live for the whole launch, and a workgroup never leaves its CU, so
+// its chunk is re-read through one XCD's L2. A chunk may be empty; the last
+// one ends at n16, so every index is below n16. `passes` is odd, as in
+// tenant_stream_kernel.
+__global__ void __launch_bounds__(kBlock)
+tenant_cache_kernel(const u64x2* __restrict__ buf, uint64_t n16, int passes,
+                    unsigned long long* __restrict__ out,
+                    unsigned long long* __restrict__ rec) {
+  const unsigned long long t0 = stamp_start();
+  const uint64_t b = blockIdx.x, grid = gridDim.x;
+  const uint64_t begin = b * n16 / grid, end = (b + 1) * n16 / grid;
+  uint64_t fold = 0;
+  for (int p = 0; p < passes; ++p) {
+    uint64_t i = begin + threadIdx.x;
+    for (; i + (kStreamUnroll - 1) * kBlock < end; i += kStreamUnroll * kBlock) {
+      uint64_t f[kStreamUnroll];
+#pragma unroll
+      for (int u = 0; u < kStreamUnroll; ++u)
+        f[u] = load_fold_cached(buf + i + u * kBlock);
+#pragma unroll
+      for (int u = 0; u < kStreamUnroll; ++u) fold ^= f[u];
+    }
+    for (; i < end; i += kBlock) fold ^= load_fold_cached(buf + i);
+    // Nothing read in one pass may stand in for a load of the next.
+    asm volatile("" ::: "memory");
+  }
+  out[b * kBlock + threadIdx.x] = fold;
+  stamp_end(rec, t0);
+}
+
 // ---- host ------------------------------------------------------------------
 
-enum class Kind { kFma, kStream };
+enum class Kind { kFma, kStream, kCache };
 
 struct Launch {
   unsigned long long t0 = 0, t1 = 0;
@@ -162,7 +207,8 @@ struct TenantResult {
   int workgroups = 0;
   uint64_t bytes = 0;
   int iters = 0, passes = 0;
-  double work_per_launch = 0.0;  // flops (fma) or bytes (stream)
+  double work_per_launch = 0.0;  // flops (fma) or bytes (stream, cache)
+  double bytes_per_cu = 0.0;     // cache only
   std::vector<Launch> launches;
   double rate = 0.0;  // median over launches: GFLOP/s or GB/s
   uint64_t checksum = 0;
@@ -179,7 +225,8 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
   // either way. (To a process started under ROC_GLOBAL_CU_MASK the runtime
   // reports only the CUs of that mask as the card's, so there the grid is 32 x
   // the process's own CUs; every rate is over the work actually launched.)
-  const int grid = kGroupsPerCu * cus;
+  const bool reads = kind != Kind::kFma;
+  const int grid = (kind == Kind::kCache ? kCacheGroupsPerCu : kGroupsPerCu) * cus;
   const size_t lanes = static_cast<size_t>(grid) * kBlock;
 
   TenantResult r;
@@ -190,13 +237,15 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     r.iters = std::min(iters, 1 << 18);
     r.work_per_launch = 2.0 * kFmaChains * static_cast<double>(lanes) * r.iters;
   } else {
-    if (bytes == 0) bytes = kGiB;
-    bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, 16), 16 * kGiB);
+    const bool cache = kind == Kind::kCache;
+    if (bytes == 0) bytes = cache ? 16 * kMiB : kGiB;
+    bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, 16), cache ? kGiB : 16 * kGiB);
     r.bytes = bytes & ~static_cast<uint64_t>(15);
-    if (passes <= 0) passes = 127;
-    passes = std::min(passes, 4095);
+    if (passes <= 0) passes = cache ? 1023 : 127;
+    passes = std::min(passes, cache ? 65535 : 4095);
     r.passes = passes | 1;  // odd: the XOR over all passes is that of one
     r.work_per_launch = static_cast<double>(r.bytes) * r.passes;
+    if (cache) r.bytes_per_cu = static_cast<double>(r.bytes) / cus;
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     r.free_bytes = free_b;
@@ -213,7 +262,7 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
 
   const uint64_t n16 = r.bytes / 16;
   DevBuf buf, out, recs;
-  if (kind == Kind::kStream) buf.alloc(r.bytes);
+  if (reads) buf.alloc(r.bytes);
   out.alloc(lanes * (kind == Kind::kFma ? sizeof(float) : sizeof(unsigned long long)));
   // One record per timed launch, and one more for the warm-up.
   std::vector<unsigned long long> h_recs(2 * static_cast<size_t>(launches + 1));
@@ -237,13 +286,17 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
       if (kind == Kind::kFma)
         hipLaunchKernelGGL(tenant_fma_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                            out.as<float>(), r.iters, 0.999f, 0.001f, rec);
-      else
+      else if (kind == Kind::kStream)
         hipLaunchKernelGGL(tenant_stream_kernel, dim3(grid), dim3(kBlock), 0, g.s,
+                           buf.as<const u64x2>(), n16, r.passes,
+                           out.as<unsigned long long>(), rec);
+      else
+        hipLaunchKernelGGL(tenant_cache_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                            buf.as<const u64x2>(), n16, r.passes,
                            out.as<unsigned long long>(), rec);
       HIP_CHECK(hipGetLastError());
     };
-    if (kind == Kind::kStream) {
+    if (reads) {
       hipLaunchKernelGGL(tenant_fill_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                          buf.as<ulonglong2>(), n16, seed);
       HIP_CHECK(hipGetLastError());
@@ -259,7 +312,7 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     HIP_CHECK(hipStreamSynchronize(g.s));
     HIP_CHECK(hipMemcpy(h_recs.data(), recs.p, h_recs.size() * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost));
-    if (kind == Kind::kStream) {
+    if (reads) {
       h_out.resize(lanes);
       HIP_CHECK(hipMemcpy(h_out.data(), out.p, lanes * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost));
@@ -302,8 +355,11 @@ void register_cotenant(py::module_& m) {
           k = Kind::kFma;
         else if (kind == "stream")
           k = Kind::kStream;
+        else if (kind == "cache")
+          k = Kind::kCache;
         else
-          throw py::value_error("cu_tenant_run: kind must be \"fma\" or \"stream\"");
+          throw py::value_error(
+              "cu_tenant_run: kind must be \"fma\", \"stream\" or \"cache\"");
         TenantResult r;
         {
           py::gil_scoped_release release;
@@ -326,6 +382,7 @@ void register_cotenant(py::module_& m) {
           d["bytes"] = r.bytes;
           d["passes"] = r.passes;
           d["checksum"] = r.checksum;
+          if (k == Kind::kCache) d["bytes_per_cu"] = r.bytes_per_cu;
         }
         d["work_per_launch"] = r.work_per_launch;
         py::list launches_out;
@@ -347,12 +404,14 @@ void register_cotenant(py::module_& m) {
       py::arg("passes") = 0, py::arg("seed") = 1,
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
-      "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\" or \"stream\", anything "
-      "else raises ValueError before the device is touched. After one untimed "
+      "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\" or "
+      "\"cache\", anything else raises ValueError before the device is "
+      "touched. After one untimed "
       "launch, `launches` (1..64) launches of the same work run back to back "
       "on one stream, each between its own pair of events; the grid is 32 x "
-      "CUs workgroups of 256 lanes whatever `mask` is, CUs being what the "
-      "device reports to this process.\n\n"
+      "CUs workgroups of 256 lanes (cache: 8 x CUs, all resident at once) "
+      "whatever `mask` is, CUs being what the device reports to this "
+      "process.\n\n"
       "fma: 16 independent FP32 FMA chains of `iters` (default 65536, at most "
       "262144) per lane, in registers. stream: every lane reads one allocation "
       "of `bytes` (default 1 GiB, rounded down to a multiple of 16, clamped to "
@@ -363,13 +422,25 @@ void register_cotenant(py::module_& m) {
       "GiB is free nothing is allocated and {skipped, bytes, free_bytes} is "
       "returned. A buffer that fits the Infinity Cache (256 MiB) measures the "
       "cache, not HBM.\n\n"
+      "cache: workgroup b of the 8 x CUs re-reads its own contiguous 16-byte "
+      "elements [b * n / grid, (b + 1) * n / grid) of one allocation of `bytes` "
+      "(default 16 MiB, half the aggregate L2; rounded down to a multiple of "
+      "16, clamped to 16 B .. 1 GiB) `passes` times (default 1023, at most "
+      "65535, an even value is raised by one) with plain 16-byte loads, four "
+      "in flight. The whole buffer is live for the whole launch and each "
+      "chunk is read through one XCD's L2. A default launch moves 16 GiB, "
+      "which a whole card reading its L2 does in 0.6 ms. Filled "
+      "and refused like stream; the result adds bytes_per_cu = bytes / "
+      "CUs.\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
       "{kind, applied_mask, tick_hz, workgroups, iters | bytes, passes, checksum, "
-      "work_per_launch: flops or bytes, launches: [{t0, t1, seconds: (t1 - t0) "
+      "[bytes_per_cu,] work_per_launch: flops or bytes, launches: [{t0, t1, "
+      "seconds: (t1 - t0) "
       "/ tick_hz, event_seconds, rate}], rate}; rates are GFLOP/s or GB/s over "
       "`seconds`, the top-level one the median over launches. checksum (stream "
-      "only) is the XOR of the words the last launch's lanes stored and equals "
+      "and cache) is the XOR of the words the last launch's lanes stored and "
+      "equals "
       "pattern_xor(seed, 0, bytes // 8) when every byte was read.");
 }
