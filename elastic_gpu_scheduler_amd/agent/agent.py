@@ -30,7 +30,9 @@ equivalent's control logic:
     in separate processes under disjoint masks, each one's rate alone and
     next to the other (agent/cotenancy.py);
   * cache_profile() — likewise for an idle card: one tenant alone, its
-    re-read rate by working-set size, which shows where the caches end.
+    re-read rate by working-set size, which shows where the caches end;
+  * chase_profile() — likewise: one tenant alone, its time per dependent
+    load by working-set size, the latency of each level of the hierarchy.
 """
 from __future__ import annotations
 
@@ -63,6 +65,10 @@ SELF_TEST_PATTERN_SEED = 0x6A09E667F3BCC908
 # Working sets of cache_profile(): below, around and above the aggregate L2
 # (32 MiB) and the Infinity Cache (256 MiB).
 CACHE_PROFILE_SIZES = tuple(m << 20 for m in (2, 8, 16, 24, 48, 128, 192, 512, 1024))
+
+# Working sets of chase_profile(): every XCD walks the whole buffer, so the
+# steps are at one XCD's L2 (4 MiB) and the Infinity Cache (256 MiB).
+CHASE_PROFILE_SIZES = tuple(m << 20 for m in (1, 2, 4, 8, 32, 64, 128, 256, 512, 1024))
 
 
 class NodeAgent:
@@ -438,7 +444,10 @@ class NodeAgent:
         re-reads a working set small enough for a cache; `windows` gives a
         kind its own iters / bytes / passes, e.g. {"cache": {"bytes": 12 <<
         20, "passes": cotenancy.cache_passes(12 << 20)}} next to the default
-        1 GiB streamer.
+        1 GiB streamer. pairs=cotenancy.CHASE_PAIRS brings in the fourth, a
+        tenant bound by the latency of dependent loads, e.g. with windows=
+        {"chase": {"bytes": 64 << 20}}; its rates are Ghop/s and its solo
+        entry adds ns_per_hop.
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched
@@ -489,6 +498,28 @@ class NodeAgent:
         ("unsupported-layout"). For an idle card."""
         from elastic_gpu_scheduler_amd.agent import cotenancy
 
+        return self._solo_profile(cotenancy.cache_profile, card, share, sizes, window)
+
+    def chase_profile(self, card: int, share: int = 50,
+                      sizes: Sequence[int] = CHASE_PROFILE_SIZES,
+                      **window: Any) -> Dict[str, Any]:
+        """One tenant holding `share` percent of `card`, alone, following a
+        chain of dependent loads through working sets of `sizes` bytes
+        (default 1 MiB .. 1 GiB), one process per size under the mask the
+        planner would grant it: where the time per hop steps up, the working
+        set has left a cache (cotenancy.chase_profile, to which `window` is
+        passed: launches, iters, timeout). Returns that report plus
+        "tenant": {core, mask, cus}.
+
+        Gated exactly as cache_profile is. For an idle card."""
+        from elastic_gpu_scheduler_amd.agent import cotenancy
+
+        return self._solo_profile(cotenancy.chase_profile, card, share, sizes, window)
+
+    def _solo_profile(self, profile, card: int, share: int, sizes: Sequence[int],
+                      window: Dict[str, Any]) -> Dict[str, Any]:
+        """cache_profile's and chase_profile's common part: the gate, the
+        scratch plan's mask for `share`, the sweep, the tenant's entry."""
         layout = self.mask_layouts().get(card)
         if not layout or not layout.get("interleaved"):
             return {"ok": False, "reason": "unsupported-layout"}
@@ -499,7 +530,7 @@ class NodeAgent:
         grant = plan.allocate(0, int(share))
         if not plan.whole_granules(grant.mask):
             return {"ok": False, "reason": "unsupported-layout"}
-        report = cotenancy.cache_profile(card, grant.mask, list(sizes), **window)
+        report = profile(card, grant.mask, list(sizes), **window)
         report["tenant"] = {"core": int(share), "mask": mask_hex(grant.mask),
                             "cus": grant.cus}
         return report

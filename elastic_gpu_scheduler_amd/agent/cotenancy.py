@@ -11,12 +11,19 @@ those that provably ran while the other tenant was running:
   * overlap()          — per launch of A, the fraction covered by B's launches;
   * run_pair()         — up to two children at once, READY / GO handshake;
   * isolation_report() — solo rates first, then the pairs, then the ratios;
-  * cache_profile()    — one tenant alone, its rate by working-set size.
+  * cache_profile()    — one tenant alone, its rate by working-set size;
+  * chase_profile()    — one tenant alone, its time per dependent load by
+                         working-set size.
 
-A tenant is one of three kinds: "fma" (registers only), "stream" (1 GiB read
-through, non-temporal) or "cache" (a working set re-read with plain loads,
-every byte of it live for the whole launch). Each kind may be given a window
-of its own, so a 12 MiB cache tenant can sit next to a 1 GiB streamer.
+A tenant is one of four kinds: "fma" (registers only), "stream" (1 GiB read
+through, non-temporal), "cache" (a working set re-read with plain loads,
+every byte of it live for the whole launch) or "chase" (every wave follows a
+chain of dependent loads, one 128-byte line in flight at a time: bound by
+latency, not by bandwidth). Each kind may be given a window of its own, so a
+12 MiB cache tenant can sit next to a 1 GiB streamer.
+
+The chase tenant's oracle is here and in closed form: chase_stride() and
+chase_checksum() state where every wave must end, in integers only.
 
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
@@ -41,12 +48,15 @@ from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 from elastic_gpu_scheduler_amd.agent.cumask import mask_hex
 from elastic_gpu_scheduler_amd.agent.wiring import ENV_CU_MASK
 
-KINDS = ("fma", "stream", "cache")
+KINDS = ("fma", "stream", "cache", "chase")
 ALL_PAIRS: Tuple[Tuple[str, str], ...] = (
     ("fma", "fma"), ("stream", "stream"), ("fma", "stream"), ("stream", "fma"))
 # The pairs that say what a neighbour does to a tenant living in a cache.
 CACHE_PAIRS: Tuple[Tuple[str, str], ...] = (
     ("cache", "cache"), ("cache", "stream"), ("stream", "cache"), ("cache", "fma"))
+# The pairs that say what a neighbour does to a tenant bound by latency.
+CHASE_PAIRS: Tuple[Tuple[str, str], ...] = (
+    ("chase", "chase"), ("chase", "stream"), ("stream", "chase"), ("chase", "fma"))
 # What may differ from tenant to tenant, or from kind to kind, within one call.
 WINDOW_KEYS = ("iters", "bytes", "passes")
 # Kinds whose result carries a checksum of the buffer they read.
@@ -111,6 +121,38 @@ def cache_passes(nbytes: int, launch_bytes: int = PAIR_LAUNCH_BYTES) -> int:
     """The odd number of passes with which a cache tenant of `nbytes` reads
     about `launch_bytes` per launch, within the probe's 1..65535."""
     return min(MAX_CACHE_PASSES, max(1, launch_bytes // max(int(nbytes), 16))) | 1
+
+
+# --- the chase tenant's oracle ------------------------------------------------
+
+def chase_stride(nodes: int) -> int:
+    """The chase tenant's hop: next(i) = (i + stride) % nodes. The first of
+    s0, s0 + 1, ... coprime to `nodes`, from s0 = nodes * 28657 // 46368 (a
+    Fibonacci ratio, about 0.618), so the chain is one cycle through every
+    node; 0 for a single node, which loops on itself."""
+    nodes = int(nodes)
+    if nodes < 1:
+        raise ValueError("a chase buffer has at least one node")
+    stride = nodes * 28657 // 46368
+    while math.gcd(stride, nodes) != 1:
+        stride += 1
+    return stride
+
+
+def chase_checksum(nbytes: int, workgroups: int, iters: int, seed: int) -> int:
+    """What a chase tenant's checksum must be: the buffer of `nbytes` (a
+    multiple of 128) is nbytes // 128 nodes; wave w of the 4 * `workgroups`
+    starts at (seed + w * nodes // W) % nodes and ends `iters` hops of
+    chase_stride(nodes) further on; each of its 64 lanes g = 64 w .. 64 w +
+    63 adds (g + 1) * (end + 1), modulo 2^64."""
+    nodes = int(nbytes) // 128
+    stride, waves = chase_stride(nodes), 4 * int(workgroups)
+    total = 0
+    for w in range(waves):
+        end = (seed + w * nodes // waves + iters * stride) % nodes
+        # the sum of g + 1 over the wave's lanes
+        total += (64 * 64 * w + 64 * 65 // 2) * (end + 1)
+    return total % (1 << 64)
 
 
 # --- child ------------------------------------------------------------------
@@ -236,7 +278,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
              ) -> Dict[str, Any]:
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
-    "fma" | "stream" | "cache"} and may carry its own "launches", "iters",
+    "fma" | "stream" | "cache" | "chase"} and may carry its own "launches", "iters",
     "bytes" and "passes" in place of the call-wide ones; `kinds`, when given,
     names the kinds instead. Every child warms up and says READY; only then
     are all told GO. Returns {"ok": True, "tenants": [the children's
@@ -350,8 +392,14 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     cache_passes(bytes), or the launch count it would need to keep up is cut
     at 64 and the neighbour's launches past its end are dropped as solo.
 
+    A chase tenant (pairs=CHASE_PAIRS) takes `bytes` and `iters`, hops per
+    wave and launch; its rates are Ghop/s, its solo entry adds ns_per_hop,
+    and its checksum is held against chase_checksum(), not against
+    `expected_checksum`, which stays the oracle of the reading kinds.
+
     ok says that the measurement is valid (every child exited 0, every
-    stream and cache checksum equals the pattern's, overlap was reached), not that the
+    stream and cache checksum equals the pattern's, every chase checksum the
+    closed form's, overlap was reached), not that the
     tenants are isolated: no interference threshold is built in. The first
     child that fails ends the report ("child-failed"): nothing further is
     started."""
@@ -386,6 +434,10 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 checksums[size] = expected_checksum(seed, size)
             if int(result["checksum"]) != checksums[size]:
                 return "bad-checksum"
+        if result["kind"] == "chase":
+            if int(result["checksum"]) != chase_checksum(
+                    result["bytes"], result["workgroups"], result["iters"], seed):
+                return "bad-checksum"
         return None
 
     for i, tenant in enumerate(tenants):
@@ -410,6 +462,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 "seconds": statistics.median(l["seconds"] for l in result["launches"]),
                 "launches": len(result["launches"]),
                 "workgroups": result.get("workgroups")}
+            if kind == "chase":
+                report["solo"][i][kind]["ns_per_hop"] = result["ns_per_hop"]
 
     for pair in pairs:
         name = "/".join(pair)
@@ -494,6 +548,46 @@ def cache_profile(card: int, mask: int, sizes: Sequence[int], *,
             "rate": result["rate"],
             "seconds": statistics.median(l["seconds"] for l in result["launches"]),
             "passes": result["passes"]})
+    return out
+
+
+def chase_profile(card: int, mask: int, sizes: Sequence[int], *,
+                  launches: int = 8, iters: int = 0, seed: int = 1,
+                  timeout: float = 120.0,
+                  spawn: Optional[Callable[..., Any]] = None) -> Dict[str, Any]:
+    """One chase tenant alone under `mask`, once per working-set size: where
+    the time per hop steps up is where the working set stops fitting a cache,
+    and each plateau is that level's dependent-load latency with one load in
+    flight per wave. One child per size, in the order given, never two at
+    once. `iters` 0 is the probe's default, 65536 hops per wave and launch.
+    Returns {"ok", "profile": [{bytes, nodes, iters, ns_per_hop, rate,
+    seconds}]}, rate in Ghop/s, ns_per_hop and seconds the median over the
+    launches.
+
+    The first child that fails ends the sweep ("child-failed"), as does one
+    that finds too little free memory; a wrong checksum (chase_checksum)
+    makes it not ok but the figures are kept. Nothing is retried."""
+    out: Dict[str, Any] = {"ok": True, "profile": []}
+    for size in sizes:
+        run = run_pair(card, [{"mask": mask, "kind": "chase", "bytes": int(size),
+                               "iters": iters}],
+                       launches=launches, seed=seed, timeout=timeout, spawn=spawn)
+        if not run["ok"]:
+            out.update(ok=False, reason=run["reason"], detail=run["detail"])
+            return out
+        result = run["tenants"][0]
+        if "skipped" in result:
+            out.update(ok=False, reason="insufficient-memory")
+            return out
+        if int(result["checksum"]) != chase_checksum(
+                result["bytes"], result["workgroups"], result["iters"], seed):
+            out["ok"] = False
+            out.setdefault("reason", "bad-checksum")
+        out["profile"].append({
+            "bytes": result["bytes"], "nodes": result["nodes"],
+            "iters": result["iters"], "ns_per_hop": result["ns_per_hop"],
+            "rate": result["rate"],
+            "seconds": statistics.median(l["seconds"] for l in result["launches"])})
     return out
 
 

@@ -20,7 +20,8 @@ is granted a CU mask sized to its share, recorded on the pod as
   elasticgpu.io/cu-mask         per-container {card, mask, cus, shared}
 --co-tenancy qualifies an idle node: per card, two tenants in separate
 processes under disjoint masks, each one's rate alone and next to the other.
---co-tenancy-cache does the same for a tenant whose working set fits a cache.
+--co-tenancy-cache does the same for a tenant whose working set fits a cache,
+--co-tenancy-chase for a tenant bound by the latency of dependent loads.
 """
 from __future__ import annotations
 
@@ -96,6 +97,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "tenant, next to the 1 GiB streamer (both ways round) "
                         "and next to an FMA tenant, and print one report per "
                         "card and size")
+    p.add_argument("--co-tenancy-chase", nargs="?", type=mib_list_arg,
+                   const=(2, 64, 1024), default=None, metavar="MIB[,MIB...]",
+                   help="with --co-tenancy: instead of the FMA and stream "
+                        "pairs, run a tenant that follows a chain of "
+                        "dependent loads through a working set of each size "
+                        "(default 2,64,1024 MiB: inside one XCD's L2, inside "
+                        "the Infinity Cache, in HBM) next to another such "
+                        "tenant, next to the 1 GiB streamer (both ways round) "
+                        "and next to an FMA tenant, and print one report per "
+                        "card and size; not together with --co-tenancy-cache")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -123,6 +134,28 @@ def main(argv=None) -> int:
     if args.co_tenancy_cache is not None and args.co_tenancy is None:
         print("--co-tenancy-cache needs --co-tenancy", file=sys.stderr)
         return 2
+
+    if args.co_tenancy_chase is not None and args.co_tenancy is None:
+        print("--co-tenancy-chase needs --co-tenancy", file=sys.stderr)
+        return 2
+    if args.co_tenancy_chase is not None and args.co_tenancy_cache is not None:
+        print("--co-tenancy-chase and --co-tenancy-cache are separate runs",
+              file=sys.stderr)
+        return 2
+
+    if args.co_tenancy_chase is not None:
+        from elastic_gpu_scheduler_amd.agent.cotenancy import CHASE_PAIRS
+
+        agent = NodeAgent(args.node or "local", client=None,
+                          prefer_source=args.source)
+        # One card and one size after another: never more than two children
+        # at once.
+        print(json.dumps({card: {str(mib): agent.verify_isolation(
+            card, args.co_tenancy, pairs=CHASE_PAIRS,
+            windows={"chase": {"bytes": mib << 20}})
+            for mib in args.co_tenancy_chase}
+            for card in sorted(agent.mask_layouts())}, indent=2))
+        return 0
 
     if args.co_tenancy_cache is not None:
         from elastic_gpu_scheduler_amd.agent.cotenancy import (CACHE_PAIRS,

@@ -2,10 +2,11 @@
 // process runs next to it.
 //   * cu_tenant_run — a series of back-to-back launches of one fixed piece of
 //     work, either register-resident FP32 FMA chains ("fma"), a read-only
-//     stream over one large allocation ("stream") or repeated reads of a
-//     working set that every workgroup keeps to itself ("cache"), each launch
-//     stamped with the device's constant-rate wall clock. The clock is the
-//     card's, not the
+//     stream over one large allocation ("stream"), repeated reads of a
+//     working set that every workgroup keeps to itself ("cache") or a walk
+//     along a chain of dependent loads, one in flight per wave ("chase"),
+//     each launch stamped with the device's constant-rate wall clock. The
+//     clock is the card's, not the
 //     process's, so two separate processes can lay their launches side by
 //     side afterwards and see which of them really ran at the same time
 //     (agent/cotenancy.py).
@@ -43,6 +44,10 @@ constexpr int kCacheGroupsPerCu = 8;  // "cache": one fill, every chunk live at 
 constexpr int kFmaChains = 16;
 constexpr int kStreamUnroll = 4;  // independent 16-byte loads in flight per lane
 constexpr int kMaxLaunches = 64;
+constexpr int kWavesPerGroup = kBlock / 64;
+constexpr uint64_t kNodeBytes = 128;  // "chase": one node is one cache line
+constexpr uint64_t kNodeWords = kNodeBytes / 8;
+constexpr int kMaxChaseIters = 1 << 22;
 constexpr uint64_t kGiB = 1ULL << 30;
 constexpr uint64_t kMiB = 1ULL << 20;
 
@@ -189,9 +194,75 @@ tenant_cache_kernel(const u64x2* __restrict__ buf, uint64_t n16, int passes,
   stamp_end(rec, t0);
 }
 
+// ---- chase -----------------------------------------------------------------
+
+// The buffer is `nodes` nodes of one 128-byte line each; every 8-byte word of
+// node i holds next(i) = (i + stride) % nodes. One 16-byte store of {next,
+// next} per element, grid-stride. n16 = 8 * nodes counts 16-byte elements;
+// stride < nodes (0 for a single node), so one subtraction wraps; all indices
+// are 64-bit.
+__global__ void __launch_bounds__(kBlock)
+tenant_chase_fill_kernel(ulonglong2* __restrict__ buf, uint64_t n16, uint64_t nodes,
+                         uint64_t stride) {
+  uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const uint64_t step = static_cast<uint64_t>(gridDim.x) * kBlock;
+  for (; i < n16; i += step) {
+    uint64_t next = i / (kNodeBytes / 16) + stride;
+    if (next >= nodes) next -= nodes;
+    ulonglong2 v;
+    v.x = next;
+    v.y = next;
+    buf[i] = v;
+  }
+}
+
+// Wave w of the W = 4 x grid starts at node (seed + w * nodes / W) % nodes
+// (`seed` arrives already reduced modulo nodes) and hops `iters` times: every
+// lane loads word (lane & 15) of the current node and takes what it loaded as
+// the next node. The sixteen words of a node are equal, so the lanes of a wave
+// stay together, but each lane's address is its own: the compiler cannot know
+// the addresses to be uniform across the wave, so the hop has to be a vector
+// memory load of one 128-byte line per wave and can never be served by the
+// scalar cache. The load is a plain one under the default cache policy, and
+// the next address depends on it, so a wave has exactly one load in flight.
+// Every value stored by the fill is below `nodes`, so every word index is
+// below 16 * nodes; a node's byte offset reaches 16 GiB and is 64-bit.
+__global__ void __launch_bounds__(kBlock)
+tenant_chase_kernel(const unsigned long long* __restrict__ buf, uint64_t nodes,
+                    uint64_t seed, int iters, unsigned long long* __restrict__ out,
+                    unsigned long long* __restrict__ rec) {
+  const uint64_t waves = static_cast<uint64_t>(gridDim.x) * kWavesPerGroup;
+  const uint64_t w = static_cast<uint64_t>(blockIdx.x) * kWavesPerGroup + threadIdx.x / 64;
+  const uint64_t word = threadIdx.x & (kNodeWords - 1);
+  uint64_t node = (seed + w * nodes / waves) % nodes;
+  const unsigned long long t0 = stamp_start();
+  for (int i = 0; i < iters; ++i) node = buf[node * kNodeWords + word];
+  out[static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x] = node;
+  stamp_end(rec, t0);
+}
+
+// The stride of the chain: the first of s0, s0 + 1, ... that is coprime to
+// `nodes`, s0 = floor(nodes * 28657 / 46368) (two Fibonacci numbers, a ratio
+// of about 0.618). Coprime, so the chain is one cycle through every node; 0
+// for a single node. Integers only: agent/cotenancy.py states the same rule
+// on its own.
+uint64_t chase_stride(uint64_t nodes) {
+  auto gcd = [](uint64_t a, uint64_t b) {
+    while (b) {
+      const uint64_t t = a % b;
+      a = b;
+      b = t;
+    }
+    return a;
+  };
+  uint64_t s = nodes * 28657 / 46368;
+  while (gcd(s, nodes) != 1) ++s;
+  return s;
+}
+
 // ---- host ------------------------------------------------------------------
 
-enum class Kind { kFma, kStream, kCache };
+enum class Kind { kFma, kStream, kCache, kChase };
 
 struct Launch {
   unsigned long long t0 = 0, t1 = 0;
@@ -207,10 +278,12 @@ struct TenantResult {
   int workgroups = 0;
   uint64_t bytes = 0;
   int iters = 0, passes = 0;
-  double work_per_launch = 0.0;  // flops (fma) or bytes (stream, cache)
+  uint64_t nodes = 0, stride = 0;  // chase only
+  double work_per_launch = 0.0;  // flops (fma), bytes (stream, cache) or hops (chase)
   double bytes_per_cu = 0.0;     // cache only
   std::vector<Launch> launches;
-  double rate = 0.0;  // median over launches: GFLOP/s or GB/s
+  double rate = 0.0;  // median over launches: GFLOP/s, GB/s or Ghop/s
+  double ns_per_hop = 0.0;  // chase only: median over launches
   uint64_t checksum = 0;
 };
 
@@ -226,7 +299,10 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
   // reports only the CUs of that mask as the card's, so there the grid is 32 x
   // the process's own CUs; every rate is over the work actually launched.)
   const bool reads = kind != Kind::kFma;
-  const int grid = (kind == Kind::kCache ? kCacheGroupsPerCu : kGroupsPerCu) * cus;
+  const bool chase = kind == Kind::kChase;
+  // "chase": one workgroup per CU, that is one wave per SIMD.
+  const int grid =
+      (chase ? 1 : kind == Kind::kCache ? kCacheGroupsPerCu : kGroupsPerCu) * cus;
   const size_t lanes = static_cast<size_t>(grid) * kBlock;
 
   TenantResult r;
@@ -238,14 +314,26 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     r.work_per_launch = 2.0 * kFmaChains * static_cast<double>(lanes) * r.iters;
   } else {
     const bool cache = kind == Kind::kCache;
-    if (bytes == 0) bytes = cache ? 16 * kMiB : kGiB;
-    bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, 16), cache ? kGiB : 16 * kGiB);
-    r.bytes = bytes & ~static_cast<uint64_t>(15);
-    if (passes <= 0) passes = cache ? 1023 : 127;
-    passes = std::min(passes, cache ? 65535 : 4095);
-    r.passes = passes | 1;  // odd: the XOR over all passes is that of one
-    r.work_per_launch = static_cast<double>(r.bytes) * r.passes;
-    if (cache) r.bytes_per_cu = static_cast<double>(r.bytes) / cus;
+    if (chase) {
+      if (bytes == 0) bytes = kGiB;
+      bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, kNodeBytes), 16 * kGiB);
+      r.bytes = bytes & ~(kNodeBytes - 1);
+      r.nodes = r.bytes / kNodeBytes;
+      r.stride = chase_stride(r.nodes);
+      if (iters <= 0) iters = 65536;
+      r.iters = std::min(iters, kMaxChaseIters);  // hops per wave and launch
+      r.work_per_launch =
+          static_cast<double>(grid) * kWavesPerGroup * static_cast<double>(r.iters);
+    } else {
+      if (bytes == 0) bytes = cache ? 16 * kMiB : kGiB;
+      bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, 16), cache ? kGiB : 16 * kGiB);
+      r.bytes = bytes & ~static_cast<uint64_t>(15);
+      if (passes <= 0) passes = cache ? 1023 : 127;
+      passes = std::min(passes, cache ? 65535 : 4095);
+      r.passes = passes | 1;  // odd: the XOR over all passes is that of one
+      r.work_per_launch = static_cast<double>(r.bytes) * r.passes;
+      if (cache) r.bytes_per_cu = static_cast<double>(r.bytes) / cus;
+    }
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     r.free_bytes = free_b;
@@ -290,13 +378,21 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
         hipLaunchKernelGGL(tenant_stream_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                            buf.as<const u64x2>(), n16, r.passes,
                            out.as<unsigned long long>(), rec);
+      else if (chase)
+        hipLaunchKernelGGL(tenant_chase_kernel, dim3(grid), dim3(kBlock), 0, g.s,
+                           buf.as<const unsigned long long>(), r.nodes, seed % r.nodes,
+                           r.iters, out.as<unsigned long long>(), rec);
       else
         hipLaunchKernelGGL(tenant_cache_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                            buf.as<const u64x2>(), n16, r.passes,
                            out.as<unsigned long long>(), rec);
       HIP_CHECK(hipGetLastError());
     };
-    if (reads) {
+    if (chase) {
+      hipLaunchKernelGGL(tenant_chase_fill_kernel, dim3(kGroupsPerCu * cus), dim3(kBlock),
+                         0, g.s, buf.as<ulonglong2>(), n16, r.nodes, r.stride);
+      HIP_CHECK(hipGetLastError());
+    } else if (reads) {
       hipLaunchKernelGGL(tenant_fill_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                          buf.as<ulonglong2>(), n16, seed);
       HIP_CHECK(hipGetLastError());
@@ -319,7 +415,12 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     }
   }  // the stream is gone before the result is looked at
 
-  for (unsigned long long w : h_out) r.checksum ^= w;  // of the last launch
+  // Of the last launch. "chase": every lane's end node weighted by its global
+  // index, both from 1 so that neither lane 0 nor node 0 drops out.
+  if (chase)
+    for (size_t g = 0; g < h_out.size(); ++g) r.checksum += (g + 1) * (h_out[g] + 1);
+  else
+    for (unsigned long long w : h_out) r.checksum ^= w;
   std::vector<double> rates;
   for (int l = 0; l < launches; ++l) {
     Launch e;
@@ -339,6 +440,12 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
   std::sort(rates.begin(), rates.end());
   const size_t n = rates.size();
   r.rate = n % 2 ? rates[n / 2] : 0.5 * (rates[n / 2 - 1] + rates[n / 2]);
+  if (chase) {
+    std::vector<double> ns;
+    for (const auto& e : r.launches) ns.push_back(e.seconds * 1e9 / r.iters);
+    std::sort(ns.begin(), ns.end());
+    r.ns_per_hop = n % 2 ? ns[n / 2] : 0.5 * (ns[n / 2 - 1] + ns[n / 2]);
+  }
   return r;
 }
 
@@ -357,9 +464,12 @@ void register_cotenant(py::module_& m) {
           k = Kind::kStream;
         else if (kind == "cache")
           k = Kind::kCache;
+        else if (kind == "chase")
+          k = Kind::kChase;
         else
           throw py::value_error(
-              "cu_tenant_run: kind must be \"fma\", \"stream\" or \"cache\"");
+              "cu_tenant_run: kind must be \"fma\", \"stream\", \"cache\" or "
+              "\"chase\"");
         TenantResult r;
         {
           py::gil_scoped_release release;
@@ -378,6 +488,12 @@ void register_cotenant(py::module_& m) {
         d["workgroups"] = r.workgroups;
         if (k == Kind::kFma) {
           d["iters"] = r.iters;
+        } else if (k == Kind::kChase) {
+          d["bytes"] = r.bytes;
+          d["nodes"] = r.nodes;
+          d["stride"] = r.stride;
+          d["iters"] = r.iters;
+          d["checksum"] = r.checksum;
         } else {
           d["bytes"] = r.bytes;
           d["passes"] = r.passes;
@@ -397,6 +513,7 @@ void register_cotenant(py::module_& m) {
         }
         d["launches"] = launches_out;
         d["rate"] = r.rate;
+        if (k == Kind::kChase) d["ns_per_hop"] = r.ns_per_hop;
         return d;
       },
       py::arg("device") = 0, py::arg("mask") = py::none(), py::arg("kind") = "fma",
@@ -404,12 +521,13 @@ void register_cotenant(py::module_& m) {
       py::arg("passes") = 0, py::arg("seed") = 1,
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
-      "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\" or "
-      "\"cache\", anything else raises ValueError before the device is "
-      "touched. After one untimed "
+      "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
+      "\"cache\" or \"chase\", anything else raises ValueError before the "
+      "device is touched. After one untimed "
       "launch, `launches` (1..64) launches of the same work run back to back "
       "on one stream, each between its own pair of events; the grid is 32 x "
-      "CUs workgroups of 256 lanes (cache: 8 x CUs, all resident at once) "
+      "CUs workgroups of 256 lanes (cache: 8 x CUs, all resident at once; "
+      "chase: 1 x CUs, one wave per SIMD) "
       "whatever `mask` is, CUs being what the device reports to this "
       "process.\n\n"
       "fma: 16 independent FP32 FMA chains of `iters` (default 65536, at most "
@@ -432,13 +550,40 @@ void register_cotenant(py::module_& m) {
       "which a whole card reading its L2 does in 0.6 ms. Filled "
       "and refused like stream; the result adds bytes_per_cu = bytes / "
       "CUs.\n\n"
+      "chase: one allocation of `bytes` (default 1 GiB, rounded down to a "
+      "multiple of 128, clamped to 128 B .. 16 GiB) is `nodes` = bytes / 128 "
+      "nodes of one 128-byte line; all sixteen 8-byte words of node i hold (i "
+      "+ `stride`) % nodes, written once on the same stream before anything "
+      "is timed. `stride` is the first of s0, s0 + 1, ... coprime to nodes, "
+      "s0 = nodes * 28657 // 46368, so the chain is a single cycle through "
+      "every node and consecutive hops land far apart (a single node loops "
+      "on itself, stride 0). Wave w of the W = 4 x CUs starts at node (`seed` "
+      "+ w * nodes // W) % nodes and hops `iters` times (hops per wave and "
+      "launch: default 65536, clamped to 1 .. 4194304; `passes` is ignored): "
+      "every lane loads word (lane & 15) of the current node with a plain "
+      "load and takes the value as the next node, so a wave has exactly one "
+      "load of one line in flight; at the end every lane stores its node. "
+      "Refused like stream. The result has bytes, nodes, stride, iters in "
+      "place of passes, work_per_launch = W * iters hops, rates in Ghop/s, "
+      "and adds ns_per_hop = the median over launches of seconds * 1e9 / "
+      "iters; its checksum is the sum over all lanes g of (g + 1) * (end node "
+      "of g + 1) modulo 2^64, which equals the closed form ((start + iters * "
+      "stride) % nodes per wave) only when every wave ended where it should "
+      "and its lanes agree. ns_per_hop is one wave's dependent-load latency "
+      "only while every workgroup is resident at once: always so for a "
+      "process started under ROC_GLOBAL_CU_MASK, whose grid is its own CUs, "
+      "but not for an in-process `mask` smaller than 1/8 of the card, under "
+      "which workgroups queue behind one another. Every XCD walks the whole "
+      "buffer, so the working set fits \"the L2\" only up to 4 MiB, one XCD's "
+      "L2, unlike the cache kind, whose chunks spread over the eight L2s.\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
       "{kind, applied_mask, tick_hz, workgroups, iters | bytes, passes, checksum, "
-      "[bytes_per_cu,] work_per_launch: flops or bytes, launches: [{t0, t1, "
+      "[bytes_per_cu,] work_per_launch: flops, bytes or hops, launches: [{t0, t1, "
       "seconds: (t1 - t0) "
-      "/ tick_hz, event_seconds, rate}], rate}; rates are GFLOP/s or GB/s over "
+      "/ tick_hz, event_seconds, rate}], rate}; rates are GFLOP/s, GB/s or "
+      "Ghop/s over "
       "`seconds`, the top-level one the median over launches. checksum (stream "
       "and cache) is the XOR of the words the last launch's lanes stored and "
       "equals "
