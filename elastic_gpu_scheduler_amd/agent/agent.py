@@ -447,7 +447,12 @@ class NodeAgent:
         1 GiB streamer. pairs=cotenancy.CHASE_PAIRS brings in the fourth, a
         tenant bound by the latency of dependent loads, e.g. with windows=
         {"chase": {"bytes": 64 << 20}}; its rates are Ghop/s and its solo
-        entry adds ns_per_hop.
+        entry adds ns_per_hop. pairs=cotenancy.MFMA_PAIRS brings in the
+        fifth, a tenant issuing bf16 MFMAs back to back from registers: the
+        one load under which the chip lowers its clock for every tenant,
+        whatever the masks. Its rates are GFLOP/s, its solo entry adds
+        clock_ghz, and its entry in a pair splits ratio into clock_ratio
+        (what the shader clock explains) and cycle_ratio (what it does not).
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched

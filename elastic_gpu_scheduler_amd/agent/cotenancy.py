@@ -25,6 +25,14 @@ latency, not by bandwidth). Each kind may be given a window of its own, so a
 The chase tenant's oracle is here and in closed form: chase_stride() and
 chase_checksum() state where every wave must end, in integers only.
 
+A fifth kind, "mfma", loads the matrix cores: every wave issues bf16 MFMAs
+back to back on operands it keeps in registers. It is kept apart from KINDS
+(MATRIX_KINDS, ALL_KINDS) because it is the one kind a CU mask cannot be
+expected to isolate: the chip lowers its shader clock under matrix load, and
+that clock is chip-wide. So its entries in a report carry the clock each run
+saw, and split a tenant's ratio into the part the clock explains and the
+part it does not. Its oracle, mfma_checksum(), is here too, in integers only.
+
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
 
@@ -33,6 +41,7 @@ Child side: python -m elastic_gpu_scheduler_amd.agent.cotenancy --child ...
 from __future__ import annotations
 
 import argparse
+import functools
 import json
 import math
 import os
@@ -57,6 +66,12 @@ CACHE_PAIRS: Tuple[Tuple[str, str], ...] = (
 # The pairs that say what a neighbour does to a tenant bound by latency.
 CHASE_PAIRS: Tuple[Tuple[str, str], ...] = (
     ("chase", "chase"), ("chase", "stream"), ("stream", "chase"), ("chase", "fma"))
+# The kind that runs on the matrix cores, and every kind there is.
+MATRIX_KINDS = ("mfma",)
+ALL_KINDS = KINDS + MATRIX_KINDS
+# The pairs that say what a neighbour does to a tenant issuing MFMAs.
+MFMA_PAIRS: Tuple[Tuple[str, str], ...] = (
+    ("mfma", "mfma"), ("mfma", "stream"), ("stream", "mfma"), ("mfma", "fma"))
 # What may differ from tenant to tenant, or from kind to kind, within one call.
 WINDOW_KEYS = ("iters", "bytes", "passes")
 # Kinds whose result carries a checksum of the buffer they read.
@@ -155,13 +170,89 @@ def chase_checksum(nbytes: int, workgroups: int, iters: int, seed: int) -> int:
     return total % (1 << 64)
 
 
+# --- the mfma tenant's oracle -------------------------------------------------
+
+MFMA_VARIANTS = 16  # operand sets; wave w uses w % 16
+_M32 = 0xFFFFFFFF
+
+
+def _mix32(x: int) -> int:
+    x &= _M32
+    x ^= x >> 16
+    x = x * 0x7FEB352D & _M32
+    x ^= x >> 15
+    x = x * 0x846CA68B & _M32
+    x ^= x >> 16
+    return x
+
+
+def _mfma_a(key: int, row: int, k: int) -> int:
+    """A[row][k] of one operand variant, -15..15."""
+    return _mix32(key ^ (row << 8) ^ k ^ 0x00A00000) % 31 - 15
+
+
+def _mfma_b(key: int, k: int, col: int) -> int:
+    """B[k][col] of one operand variant, -15..15."""
+    return _mix32(key ^ (k << 8) ^ col ^ 0x00B00000) % 31 - 15
+
+
+def _mfma_product(seed: int, variant: int) -> List[List[int]]:
+    """The 64 x 64 product one step adds to a wave's tile: A (64 x 16) times
+    B (16 x 64) of `variant`, hashed from the low 32 bits of `seed`."""
+    key = _mix32((seed & _M32) ^ (variant * 0x9E3779B1 & _M32))
+    a = [[_mfma_a(key, row, k) for k in range(16)] for row in range(64)]
+    b = [[_mfma_b(key, k, col) for col in range(64)] for k in range(16)]
+    cols = [[b[k][col] for k in range(16)] for col in range(64)]
+    return [[sum(x * y for x, y in zip(a[row], cols[col])) for col in range(64)]
+            for row in range(64)]
+
+
+@functools.lru_cache(maxsize=8)
+def _mfma_lane_sums(seed32: int) -> Tuple[Tuple[int, ...], ...]:
+    """Per variant and lane, what one step adds to the lane's fold: lane r =
+    lane & 31, h = lane >> 5 holds, in register reg of accumulator (m, n),
+    row 32 m + (reg & 3) + 8 (reg >> 2) + 4 h of column 32 n + r, and weighs
+    it by 1 + reg + 16 (2 m + n)."""
+    out = []
+    for variant in range(MFMA_VARIANTS):
+        p = _mfma_product(seed32, variant)
+        lanes = []
+        for lane in range(64):
+            r, h = lane & 31, lane >> 5
+            lanes.append(sum(
+                p[32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * h][32 * n + r]
+                * (1 + reg + 16 * (2 * m + n))
+                for m in range(2) for n in range(2) for reg in range(16)))
+        out.append(tuple(lanes))
+    return tuple(out)
+
+
+def mfma_checksum(workgroups: int, iters: int, seed: int) -> int:
+    """What an mfma tenant's checksum must be. Wave w of the 4 * `workgroups`
+    multiplies variant w % 16 of the operands, small integers hashed from the
+    low 32 bits of `seed`, `iters` times into its 64 x 64 tile, and every
+    lane folds its 64 accumulator registers, weighted, into one sum. The
+    accumulators are exact and every fold is linear in the number of steps,
+    so a lane's sum is iters times what one step adds; lane g = 64 w + lane
+    adds (g + 1) times its sum, modulo 2^64."""
+    sums = _mfma_lane_sums(int(seed) & _M32)
+    waves = 4 * int(workgroups)
+    total = 0
+    for variant, lanes in enumerate(sums):
+        mine = range(variant, waves, MFMA_VARIANTS)  # the waves of this variant
+        # the sum over them of (64 w + lane + 1) * lanes[lane]
+        total += 64 * sum(mine) * sum(lanes) + len(mine) * sum(
+            (lane + 1) * s for lane, s in enumerate(lanes))
+    return total * int(iters) % (1 << 64)
+
+
 # --- child ------------------------------------------------------------------
 
 def _child_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="cotenancy", description=__doc__)
     p.add_argument("--child", action="store_true", required=True)
     p.add_argument("--device", type=int, default=0)
-    p.add_argument("--kind", choices=KINDS, default="fma")
+    p.add_argument("--kind", choices=ALL_KINDS, default="fma")
     p.add_argument("--launches", type=int, default=8)
     p.add_argument("--iters", type=int, default=0)
     p.add_argument("--bytes", type=int, default=0)
@@ -278,7 +369,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
              ) -> Dict[str, Any]:
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
-    "fma" | "stream" | "cache" | "chase"} and may carry its own "launches", "iters",
+    "fma" | "stream" | "cache" | "chase" | "mfma"} and may carry its own "launches", "iters",
     "bytes" and "passes" in place of the call-wide ones; `kinds`, when given,
     names the kinds instead. Every child warms up and says READY; only then
     are all told GO. Returns {"ok": True, "tenants": [the children's
@@ -298,7 +389,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     try:
         for i, tenant in enumerate(tenants):
             kind = kinds[i] if kinds is not None else tenant["kind"]
-            if kind not in KINDS:
+            if kind not in ALL_KINDS:
                 raise ValueError(f"unknown tenant kind {kind!r}")
             env = dict(os.environ)
             env[ENV_CU_MASK] = mask_hex(int(tenant["mask"]))
@@ -397,20 +488,32 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     and its checksum is held against chase_checksum(), not against
     `expected_checksum`, which stays the oracle of the reading kinds.
 
+    An mfma tenant (pairs=MFMA_PAIRS) takes `iters`, steps of four MFMAs per
+    wave and launch; its rates are GFLOP/s and its checksum is held against
+    mfma_checksum(). Its solo entry adds clock_ghz, the shader clock it ran
+    at, and its entry in a pair adds solo_clock_ghz, contended_clock_ghz
+    (the median over the contended launches), clock_ratio = contended clock
+    / solo clock and cycle_ratio = ratio / clock_ratio. The chip lowers its
+    clock under matrix load for the whole chip, whatever the masks, so
+    clock_ratio is the part of a slowdown that the clock explains and
+    cycle_ratio the part that it does not: a tenant slowed only by the
+    neighbour's effect on the clock has cycle_ratio 1.
+
     ok says that the measurement is valid (every child exited 0, every
-    stream and cache checksum equals the pattern's, every chase checksum the
-    closed form's, overlap was reached), not that the
-    tenants are isolated: no interference threshold is built in. The first
+    stream and cache checksum equals the pattern's, every chase and mfma
+    checksum the closed form's, overlap was reached), not that the
+    tenants are isolated: no interference threshold is built in, on ratio,
+    clock_ratio or cycle_ratio. The first
     child that fails ends the report ("child-failed"): nothing further is
     started."""
     if len(tenants) != 2:
         raise ValueError("isolation_report takes two tenants")
     for pair in pairs:
-        if len(pair) != 2 or any(k not in KINDS for k in pair):
+        if len(pair) != 2 or any(k not in ALL_KINDS for k in pair):
             raise ValueError(f"not a pair of tenant kinds: {pair!r}")
     windows = {kind: dict(w) for kind, w in (windows or {}).items()}
     for kind, w in windows.items():
-        if kind not in KINDS or any(k not in WINDOW_KEYS for k in w):
+        if kind not in ALL_KINDS or any(k not in WINDOW_KEYS for k in w):
             raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
     expected_checksum = expected_checksum or _pattern_checksum
     window = {"iters": iters, "bytes": bytes, "passes": passes, "seed": seed,
@@ -438,10 +541,14 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
             if int(result["checksum"]) != chase_checksum(
                     result["bytes"], result["workgroups"], result["iters"], seed):
                 return "bad-checksum"
+        if result["kind"] in MATRIX_KINDS:
+            if int(result["checksum"]) != mfma_checksum(
+                    result["workgroups"], result["iters"], seed):
+                return "bad-checksum"
         return None
 
     for i, tenant in enumerate(tenants):
-        for kind in KINDS:
+        for kind in ALL_KINDS:
             if not any(pair[i] == kind for pair in pairs):
                 continue
             run = run_pair(card, [{"mask": tenant["mask"], "kind": kind,
@@ -464,6 +571,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 "workgroups": result.get("workgroups")}
             if kind == "chase":
                 report["solo"][i][kind]["ns_per_hop"] = result["ns_per_hop"]
+            if kind in MATRIX_KINDS:
+                report["solo"][i][kind]["clock_ghz"] = result["clock_ghz"]
 
     for pair in pairs:
         name = "/".join(pair)
@@ -499,6 +608,13 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
             else:
                 t["contended_rate"] = statistics.median(rates)
                 t["ratio"] = t["contended_rate"] / solo_rate
+                if pair[i] in MATRIX_KINDS:
+                    clocks = [l["clock_ghz"] for l, lab in zip(mine, labels)
+                              if lab == "contended"]
+                    t["solo_clock_ghz"] = report["solo"][i][pair[i]]["clock_ghz"]
+                    t["contended_clock_ghz"] = statistics.median(clocks)
+                    t["clock_ratio"] = t["contended_clock_ghz"] / t["solo_clock_ghz"]
+                    t["cycle_ratio"] = t["ratio"] / t["clock_ratio"]
             if why:
                 t["reason"] = why
                 entry["ok"] = False

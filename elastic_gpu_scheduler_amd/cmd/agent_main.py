@@ -21,7 +21,9 @@ is granted a CU mask sized to its share, recorded on the pod as
 --co-tenancy qualifies an idle node: per card, two tenants in separate
 processes under disjoint masks, each one's rate alone and next to the other.
 --co-tenancy-cache does the same for a tenant whose working set fits a cache,
---co-tenancy-chase for a tenant bound by the latency of dependent loads.
+--co-tenancy-chase for a tenant bound by the latency of dependent loads,
+--co-tenancy-mfma for a tenant on the matrix cores, whose clock is the
+chip's and follows no mask.
 """
 from __future__ import annotations
 
@@ -107,6 +109,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "tenant, next to the 1 GiB streamer (both ways round) "
                         "and next to an FMA tenant, and print one report per "
                         "card and size; not together with --co-tenancy-cache")
+    p.add_argument("--co-tenancy-mfma", action="store_true",
+                   help="with --co-tenancy: instead of the FMA and stream "
+                        "pairs, run a tenant that issues bf16 MFMAs back to "
+                        "back from registers next to another such tenant, "
+                        "next to the 1 GiB streamer (both ways round) and "
+                        "next to an FMA tenant, and print one report per "
+                        "card: each ratio with the part of it that the shader "
+                        "clock explains (clock_ratio) and the part that it "
+                        "does not (cycle_ratio); not together with "
+                        "--co-tenancy-cache or --co-tenancy-chase")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -142,6 +154,27 @@ def main(argv=None) -> int:
         print("--co-tenancy-chase and --co-tenancy-cache are separate runs",
               file=sys.stderr)
         return 2
+
+    if args.co_tenancy_mfma and args.co_tenancy is None:
+        print("--co-tenancy-mfma needs --co-tenancy", file=sys.stderr)
+        return 2
+    for name, other in (("--co-tenancy-cache", args.co_tenancy_cache),
+                        ("--co-tenancy-chase", args.co_tenancy_chase)):
+        if args.co_tenancy_mfma and other is not None:
+            print(f"--co-tenancy-mfma and {name} are separate runs",
+                  file=sys.stderr)
+            return 2
+
+    if args.co_tenancy_mfma:
+        from elastic_gpu_scheduler_amd.agent.cotenancy import MFMA_PAIRS
+
+        agent = NodeAgent(args.node or "local", client=None,
+                          prefer_source=args.source)
+        # One card after another: never more than two children at once.
+        print(json.dumps({card: agent.verify_isolation(
+            card, args.co_tenancy, pairs=MFMA_PAIRS)
+            for card in sorted(agent.mask_layouts())}, indent=2))
+        return 0
 
     if args.co_tenancy_chase is not None:
         from elastic_gpu_scheduler_amd.agent.cotenancy import CHASE_PAIRS

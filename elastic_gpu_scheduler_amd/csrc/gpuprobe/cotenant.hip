@@ -3,8 +3,9 @@
 //   * cu_tenant_run — a series of back-to-back launches of one fixed piece of
 //     work, either register-resident FP32 FMA chains ("fma"), a read-only
 //     stream over one large allocation ("stream"), repeated reads of a
-//     working set that every workgroup keeps to itself ("cache") or a walk
-//     along a chain of dependent loads, one in flight per wave ("chase"),
+//     working set that every workgroup keeps to itself ("cache"), a walk
+//     along a chain of dependent loads, one in flight per wave ("chase"), or
+//     bf16 MFMAs issued back to back on operands held in registers ("mfma"),
 //     each launch stamped with the device's constant-rate wall clock. The
 //     clock is the card's, not the
 //     process's, so two separate processes can lay their launches side by
@@ -48,6 +49,11 @@ constexpr int kWavesPerGroup = kBlock / 64;
 constexpr uint64_t kNodeBytes = 128;  // "chase": one node is one cache line
 constexpr uint64_t kNodeWords = kNodeBytes / 8;
 constexpr int kMaxChaseIters = 1 << 22;
+constexpr int kMfmaGroupsPerCu = 8;  // "mfma": one wave per SIMD already fills the pipe
+constexpr int kMfmaVariants = 16;    // operand sets; wave w uses w % 16
+constexpr int kMfmaChunk = 2048;     // steps between two folds of the accumulators
+constexpr int kMaxMfmaIters = 1 << 20;
+constexpr double kMfmaFlops = 2.0 * 32 * 32 * 16;  // one 32x32x16 MFMA
 constexpr uint64_t kGiB = 1ULL << 30;
 constexpr uint64_t kMiB = 1ULL << 20;
 
@@ -260,13 +266,118 @@ uint64_t chase_stride(uint64_t nodes) {
   return s;
 }
 
+// ---- mfma ------------------------------------------------------------------
+
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using short8 = __attribute__((ext_vector_type(8))) short;
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+__device__ inline uint32_t mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 15;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// A[row][k] and B[k][col] of one operand variant, both in -15..15. Hashed, so
+// neither is symmetric in its two indices. agent/cotenancy.py states the same
+// rule on its own.
+__device__ inline int mfma_a_elem(uint32_t key, uint32_t row, uint32_t k) {
+  return static_cast<int>(mix32(key ^ (row << 8) ^ k ^ 0x00A00000u) % 31u) - 15;
+}
+__device__ inline int mfma_b_elem(uint32_t key, uint32_t k, uint32_t col) {
+  return static_cast<int>(mix32(key ^ (k << 8) ^ col ^ 0x00B00000u) % 31u) - 15;
+}
+
+// Small integers are exact in bf16: the bf16 is the float's upper half.
+__device__ inline short to_bf16_bits(int v) {
+  return static_cast<short>(__float_as_uint(static_cast<float>(v)) >> 16);
+}
+
+// Every wave owns a 64x64 output tile, 2 x 2 accumulators of 32x32, and keeps
+// two A fragments (rows 32m + r) and two B fragments (columns 32n + r) of K =
+// 16 in registers: lane r = lane & 31, h = lane >> 5 holds A[r][8h + j] and
+// B[8h + j][r], and output register reg is row (reg & 3) + 8 * (reg >> 2) + 4h
+// of column r. The fragments are built once, before the start stamp, from
+// variant (global wave) % 16 of the hashes above. One step is the four MFMAs
+// acc[m][n] += A_m x B_n; `iters` steps run in chunks of at most kMfmaChunk.
+// A chunk starts from zero accumulators and ends with every lane folding its
+// 64 registers into a 64-bit sum, each weighted by 1 + reg + 16 * (2m + n).
+// |A x B| <= 16 * 225 = 3600 per step and 2048 * 3600 < 2^23, so every partial
+// sum is exact in f32, its conversion to int is exact, and the fold is linear
+// in the number of steps. Nothing is read from memory between the stamps.
+//
+// clk is the launch's {sum of shader cycles, sum of wall ticks}: thread 0 of
+// every workgroup reads s_memtime next to each end of its wall-clock interval
+// and adds both differences. cycles / ticks x tick_hz is the shader clock the
+// launch ran at, averaged over its workgroups.
+__global__ void __launch_bounds__(kBlock)
+tenant_mfma_kernel(uint32_t seed32, int iters, unsigned long long* __restrict__ out,
+                   unsigned long long* __restrict__ rec,
+                   unsigned long long* __restrict__ clk) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = lane & 31u, h = lane >> 5;
+  const uint32_t w = blockIdx.x * kWavesPerGroup + threadIdx.x / 64;
+  const uint32_t key = mix32(seed32 ^ ((w % kMfmaVariants) * 0x9E3779B1u));
+  bf16x8 a[2], b[2];
+#pragma unroll
+  for (uint32_t t = 0; t < 2; ++t) {
+    short8 af, bf;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) {
+      af[j] = to_bf16_bits(mfma_a_elem(key, 32 * t + r, 8 * h + j));
+      bf[j] = to_bf16_bits(mfma_b_elem(key, 8 * h + j, 32 * t + r));
+    }
+    a[t] = __builtin_bit_cast(bf16x8, af);
+    b[t] = __builtin_bit_cast(bf16x8, bf);
+  }
+  // The fragments are in their registers before either clock is read.
+  asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  const unsigned long long t0 = stamp_start();
+  uint64_t fold = 0;
+  for (int done = 0; done < iters; done += kMfmaChunk) {
+    const int steps = min(iters - done, kMfmaChunk);
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) acc[t >> 1][t & 1][reg] = 0.0f;
+    for (int i = 0; i < steps; ++i) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        acc[t >> 1][t & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a[t >> 1], b[t & 1], acc[t >> 1][t & 1], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg)
+        fold += static_cast<uint64_t>(static_cast<int64_t>(
+                    static_cast<int>(acc[t >> 1][t & 1][reg]))) *
+                static_cast<uint64_t>(1 + reg + 16 * t);
+  }
+  out[static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x] = fold;
+  stamp_end(rec, t0);
+  if (threadIdx.x == 0) {
+    const unsigned long long c1 = __builtin_amdgcn_s_memtime();
+    const unsigned long long t1 = wall_clock64();
+    atomicAdd(&clk[0], c1 - c0);
+    atomicAdd(&clk[1], t1 - t0);
+  }
+}
+
 // ---- host ------------------------------------------------------------------
 
-enum class Kind { kFma, kStream, kCache, kChase };
+enum class Kind { kFma, kStream, kCache, kChase, kMfma };
 
 struct Launch {
   unsigned long long t0 = 0, t1 = 0;
   double seconds = 0.0, event_seconds = 0.0, rate = 0.0;
+  unsigned long long cycles = 0, ticks = 0;  // mfma only
+  double clock_ghz = 0.0;                    // mfma only
 };
 
 struct TenantResult {
@@ -279,11 +390,12 @@ struct TenantResult {
   uint64_t bytes = 0;
   int iters = 0, passes = 0;
   uint64_t nodes = 0, stride = 0;  // chase only
-  double work_per_launch = 0.0;  // flops (fma), bytes (stream, cache) or hops (chase)
+  double work_per_launch = 0.0;  // flops (fma, mfma), bytes (stream, cache) or hops (chase)
   double bytes_per_cu = 0.0;     // cache only
   std::vector<Launch> launches;
   double rate = 0.0;  // median over launches: GFLOP/s, GB/s or Ghop/s
   double ns_per_hop = 0.0;  // chase only: median over launches
+  double clock_ghz = 0.0;   // mfma only: median over launches
   uint64_t checksum = 0;
 };
 
@@ -298,11 +410,15 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
   // either way. (To a process started under ROC_GLOBAL_CU_MASK the runtime
   // reports only the CUs of that mask as the card's, so there the grid is 32 x
   // the process's own CUs; every rate is over the work actually launched.)
-  const bool reads = kind != Kind::kFma;
+  const bool mfma = kind == Kind::kMfma;
+  const bool reads = kind != Kind::kFma && !mfma;
   const bool chase = kind == Kind::kChase;
   // "chase": one workgroup per CU, that is one wave per SIMD.
-  const int grid =
-      (chase ? 1 : kind == Kind::kCache ? kCacheGroupsPerCu : kGroupsPerCu) * cus;
+  const int grid = (chase  ? 1
+                    : mfma ? kMfmaGroupsPerCu
+                    : kind == Kind::kCache ? kCacheGroupsPerCu
+                                           : kGroupsPerCu) *
+                   cus;
   const size_t lanes = static_cast<size_t>(grid) * kBlock;
 
   TenantResult r;
@@ -312,6 +428,11 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     if (iters <= 0) iters = 65536;
     r.iters = std::min(iters, 1 << 18);
     r.work_per_launch = 2.0 * kFmaChains * static_cast<double>(lanes) * r.iters;
+  } else if (mfma) {
+    if (iters <= 0) iters = 32768;
+    r.iters = std::min(iters, kMaxMfmaIters);  // steps of four MFMAs per wave and launch
+    r.work_per_launch = static_cast<double>(grid) * kWavesPerGroup *
+                        static_cast<double>(r.iters) * 4.0 * kMfmaFlops;
   } else {
     const bool cache = kind == Kind::kCache;
     if (chase) {
@@ -361,6 +482,14 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
   recs.alloc(h_recs.size() * sizeof(unsigned long long));
   HIP_CHECK(hipMemcpy(recs.p, h_recs.data(), h_recs.size() * sizeof(unsigned long long),
                       hipMemcpyHostToDevice));
+  // "mfma": {sum of shader cycles, sum of wall ticks} per launch, from zero.
+  DevBuf clks;
+  std::vector<unsigned long long> h_clks(mfma ? h_recs.size() : 0, 0ULL);
+  if (mfma) {
+    clks.alloc(h_clks.size() * sizeof(unsigned long long));
+    HIP_CHECK(hipMemcpy(clks.p, h_clks.data(), h_clks.size() * sizeof(unsigned long long),
+                        hipMemcpyHostToDevice));
+  }
   HIP_CHECK(hipDeviceSynchronize());
   std::vector<EventGuard> ev(2 * static_cast<size_t>(launches));
   for (auto& e : ev) e.create();
@@ -374,6 +503,11 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
       if (kind == Kind::kFma)
         hipLaunchKernelGGL(tenant_fma_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                            out.as<float>(), r.iters, 0.999f, 0.001f, rec);
+      else if (mfma)
+        hipLaunchKernelGGL(tenant_mfma_kernel, dim3(grid), dim3(kBlock), 0, g.s,
+                           static_cast<uint32_t>(seed), r.iters,
+                           out.as<unsigned long long>(), rec,
+                           clks.as<unsigned long long>() + 2 * slot);
       else if (kind == Kind::kStream)
         hipLaunchKernelGGL(tenant_stream_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                            buf.as<const u64x2>(), n16, r.passes,
@@ -408,7 +542,10 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     HIP_CHECK(hipStreamSynchronize(g.s));
     HIP_CHECK(hipMemcpy(h_recs.data(), recs.p, h_recs.size() * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost));
-    if (reads) {
+    if (mfma)
+      HIP_CHECK(hipMemcpy(h_clks.data(), clks.p, h_clks.size() * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost));
+    if (reads || mfma) {
       h_out.resize(lanes);
       HIP_CHECK(hipMemcpy(h_out.data(), out.p, lanes * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost));
@@ -417,8 +554,11 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
 
   // Of the last launch. "chase": every lane's end node weighted by its global
   // index, both from 1 so that neither lane 0 nor node 0 drops out.
+  // "mfma": every lane's fold weighted likewise.
   if (chase)
     for (size_t g = 0; g < h_out.size(); ++g) r.checksum += (g + 1) * (h_out[g] + 1);
+  else if (mfma)
+    for (size_t g = 0; g < h_out.size(); ++g) r.checksum += (g + 1) * h_out[g];
   else
     for (unsigned long long w : h_out) r.checksum ^= w;
   std::vector<double> rates;
@@ -434,6 +574,15 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * l].e, ev[2 * l + 1].e));
     e.event_seconds = static_cast<double>(ms) * 1e-3;
     e.rate = r.work_per_launch / e.seconds / 1e9;
+    if (mfma) {
+      e.cycles = h_clks[2 * l];
+      e.ticks = h_clks[2 * l + 1];
+      if (e.ticks == 0)
+        throw std::runtime_error("cu_tenant_run: launch " + std::to_string(l) +
+                                 " left no usable cycle record");
+      e.clock_ghz = static_cast<double>(e.cycles) / static_cast<double>(e.ticks) *
+                    r.tick_hz / 1e9;
+    }
     rates.push_back(e.rate);
     r.launches.push_back(e);
   }
@@ -445,6 +594,12 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     for (const auto& e : r.launches) ns.push_back(e.seconds * 1e9 / r.iters);
     std::sort(ns.begin(), ns.end());
     r.ns_per_hop = n % 2 ? ns[n / 2] : 0.5 * (ns[n / 2 - 1] + ns[n / 2]);
+  }
+  if (mfma) {
+    std::vector<double> ghz;
+    for (const auto& e : r.launches) ghz.push_back(e.clock_ghz);
+    std::sort(ghz.begin(), ghz.end());
+    r.clock_ghz = n % 2 ? ghz[n / 2] : 0.5 * (ghz[n / 2 - 1] + ghz[n / 2]);
   }
   return r;
 }
@@ -466,10 +621,12 @@ void register_cotenant(py::module_& m) {
           k = Kind::kCache;
         else if (kind == "chase")
           k = Kind::kChase;
+        else if (kind == "mfma")
+          k = Kind::kMfma;
         else
           throw py::value_error(
-              "cu_tenant_run: kind must be \"fma\", \"stream\", \"cache\" or "
-              "\"chase\"");
+              "cu_tenant_run: kind must be \"fma\", \"stream\", \"cache\", "
+              "\"chase\" or \"mfma\"");
         TenantResult r;
         {
           py::gil_scoped_release release;
@@ -488,6 +645,9 @@ void register_cotenant(py::module_& m) {
         d["workgroups"] = r.workgroups;
         if (k == Kind::kFma) {
           d["iters"] = r.iters;
+        } else if (k == Kind::kMfma) {
+          d["iters"] = r.iters;
+          d["checksum"] = r.checksum;
         } else if (k == Kind::kChase) {
           d["bytes"] = r.bytes;
           d["nodes"] = r.nodes;
@@ -509,11 +669,17 @@ void register_cotenant(py::module_& m) {
           l["seconds"] = e.seconds;
           l["event_seconds"] = e.event_seconds;
           l["rate"] = e.rate;
+          if (k == Kind::kMfma) {
+            l["cycles"] = e.cycles;
+            l["ticks"] = e.ticks;
+            l["clock_ghz"] = e.clock_ghz;
+          }
           launches_out.append(l);
         }
         d["launches"] = launches_out;
         d["rate"] = r.rate;
         if (k == Kind::kChase) d["ns_per_hop"] = r.ns_per_hop;
+        if (k == Kind::kMfma) d["clock_ghz"] = r.clock_ghz;
         return d;
       },
       py::arg("device") = 0, py::arg("mask") = py::none(), py::arg("kind") = "fma",
@@ -522,12 +688,12 @@ void register_cotenant(py::module_& m) {
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
-      "\"cache\" or \"chase\", anything else raises ValueError before the "
-      "device is touched. After one untimed "
+      "\"cache\", \"chase\" or \"mfma\", anything else raises ValueError "
+      "before the device is touched. After one untimed "
       "launch, `launches` (1..64) launches of the same work run back to back "
       "on one stream, each between its own pair of events; the grid is 32 x "
       "CUs workgroups of 256 lanes (cache: 8 x CUs, all resident at once; "
-      "chase: 1 x CUs, one wave per SIMD) "
+      "chase: 1 x CUs, one wave per SIMD; mfma: 8 x CUs) "
       "whatever `mask` is, CUs being what the device reports to this "
       "process.\n\n"
       "fma: 16 independent FP32 FMA chains of `iters` (default 65536, at most "
@@ -576,13 +742,46 @@ void register_cotenant(py::module_& m) {
       "which workgroups queue behind one another. Every XCD walks the whole "
       "buffer, so the working set fits \"the L2\" only up to 4 MiB, one XCD's "
       "L2, unlike the cache kind, whose chunks spread over the eight L2s.\n\n"
+      "mfma: every wave of the 8 x CUs workgroups owns a 64 x 64 output tile "
+      "as 2 x 2 accumulators of 32 x 32 and keeps two A and two B fragments "
+      "of K = 16 in registers; one step is the four v_mfma_f32_32x32x16_bf16 "
+      "acc[m][n] += A_m x B_n, and a wave runs `iters` steps per launch "
+      "(default 32768, clamped to 1 .. 1048576; `bytes` and `passes` are "
+      "ignored, nothing is allocated and nothing refused). One wave per SIMD "
+      "already issues MFMAs back to back, so the rate does not depend on how "
+      "many of the eight workgroups are resident. The operands are small "
+      "integers, -15 .. 15, exact in bf16, hashed from the low 32 bits of "
+      "`seed` and the wave's variant w % 16 before anything is timed: "
+      "A[row][k] = mix32(key ^ row << 8 ^ k ^ 0xA00000) % 31 - 15, B[k][col] "
+      "likewise with 0xB00000 and k << 8 ^ col, key = mix32(seed32 ^ (w % 16) "
+      "* 0x9E3779B1). Steps run in chunks of at most 2048 from zero "
+      "accumulators, so every partial sum stays below 2^23 and is exact in "
+      "f32; after a chunk every lane adds its 64 accumulator registers, as "
+      "integers weighted by 1 + reg + 16 * (2m + n), to a 64-bit sum that it "
+      "stores at the end. The result has iters, work_per_launch = waves * "
+      "iters * 4 * 32768 flops, rates in GFLOP/s, and checksum = the sum over "
+      "all lanes g of (g + 1) * (sum of g) modulo 2^64, which equals the "
+      "closed form (agent/cotenancy.py, mfma_checksum) only when every MFMA "
+      "of every wave gave the exact product. Thread 0 of every workgroup "
+      "also reads the shader-cycle counter (s_memtime) at both ends of its "
+      "wall-clock interval; a launch entry adds cycles and ticks, both "
+      "summed over the workgroups, and clock_ghz = cycles / ticks * tick_hz "
+      "/ 1e9, the shader clock the launch ran at, and the result adds "
+      "clock_ghz, the median over launches. The chip lowers its shader clock "
+      "under matrix load, chip-wide and whatever the CU mask, and how far "
+      "depends on the data: the clock it holds under these small integers "
+      "may differ from the one it holds under a real GEMM's operands "
+      "(all-zero operands have been seen to run 19 % faster than random "
+      "ones at equal cycles), which is why the result reports the clock it "
+      "saw and not only the rate.\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
       "{kind, applied_mask, tick_hz, workgroups, iters | bytes, passes, checksum, "
       "[bytes_per_cu,] work_per_launch: flops, bytes or hops, launches: [{t0, t1, "
       "seconds: (t1 - t0) "
-      "/ tick_hz, event_seconds, rate}], rate}; rates are GFLOP/s, GB/s or "
+      "/ tick_hz, event_seconds, rate[, cycles, ticks, clock_ghz]}], rate[, "
+      "clock_ghz]}; rates are GFLOP/s, GB/s or "
       "Ghop/s over "
       "`seconds`, the top-level one the median over launches. checksum (stream "
       "and cache) is the XOR of the words the last launch's lanes stored and "
