@@ -437,7 +437,8 @@ class NodeAgent:
         processes under the masks the planner would grant them, exactly as
         containers are wired: each tenant's FMA and HBM-stream rate alone and
         while the other runs (cotenancy.isolation_report, to which `window`
-        is passed: pairs, launches, iters, bytes, passes, timeout, windows).
+        is passed: pairs, launches, iters, bytes, passes, timeout, windows,
+        form).
         Returns that report plus "tenants": [{core, mask, cus}].
 
         pairs=cotenancy.CACHE_PAIRS brings in the third kind, a tenant that
@@ -453,6 +454,11 @@ class NodeAgent:
         whatever the masks. Its rates are GFLOP/s, its solo entry adds
         clock_ghz, and its entry in a pair splits ratio into clock_ratio
         (what the shader clock explains) and cycle_ratio (what it does not).
+        form= (one of cotenancy.MFMA_FORMS: "bf16", "fp8", "mxfp8", "mxfp4")
+        names the instruction the mfma tenants issue in place of the bf16
+        one; their entries then add "form". For two tenants of different
+        forms, such as bf16 beside mxfp4, call cotenancy.isolation_report
+        with a "form" in each tenant.
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched

@@ -32,6 +32,9 @@ expected to isolate: the chip lowers its shader clock under matrix load, and
 that clock is chip-wide. So its entries in a report carry the clock each run
 saw, and split a tenant's ratio into the part the clock explains and the
 part it does not. Its oracle, mfma_checksum(), is here too, in integers only.
+The kind has a form (MFMA_FORMS): the bf16 instruction by default, or its fp8
+twin, or the block-scaled MXFP8 and MXFP4 ones that inference tenants run,
+2 x and 4 x the bf16 work per clock through the same pipe.
 
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
@@ -173,6 +176,21 @@ def chase_checksum(nbytes: int, workgroups: int, iters: int, seed: int) -> int:
 # --- the mfma tenant's oracle -------------------------------------------------
 
 MFMA_VARIANTS = 16  # operand sets; wave w uses w % 16
+# The instruction an mfma tenant issues: "bf16" v_mfma_f32_32x32x16_bf16,
+# "fp8" its e4m3 twin, "mxfp8" and "mxfp4" the block-scaled 32x32x64 with e4m3
+# and e2m1 operands. Position is the form's id in the probe.
+MFMA_FORMS = ("bf16", "fp8", "mxfp8", "mxfp4")
+# Per form, as in csrc/gpuprobe/cotenant.hip: the K of one MFMA, its flop,
+# the steps between two folds and the steps of a default launch.
+MFMA_FORM_TABLE: Dict[str, Dict[str, int]] = {
+    "bf16": {"k": 16, "flop": 32768, "chunk": 2048, "iters": 32768},
+    "fp8": {"k": 16, "flop": 32768, "chunk": 2048, "iters": 32768},
+    "mxfp8": {"k": 64, "flop": 131072, "chunk": 512, "iters": 16384},
+    "mxfp4": {"k": 64, "flop": 131072, "chunk": 256, "iters": 32768},
+}
+# Twice the magnitude of e2m1 code & 7 (0, 0.5, 1, 1.5, 2, 3, 4, 6): the mxfp4
+# scales are 2 or 4, so every effective element is an integer.
+_E2M1_TWICE = (0, 1, 2, 3, 4, 6, 8, 12)
 _M32 = 0xFFFFFFFF
 
 
@@ -186,36 +204,59 @@ def _mix32(x: int) -> int:
     return x
 
 
-def _mfma_a(key: int, row: int, k: int) -> int:
-    """A[row][k] of one operand variant, -15..15."""
-    return _mix32(key ^ (row << 8) ^ k ^ 0x00A00000) % 31 - 15
+def _mfma_elem(form: int, h: int, scale_bit: int, is_a: bool) -> int:
+    """The effective integer a hashed element stands for in form id `form`:
+    bf16 and fp8 h % 31 - 15; mxfp8 (h % 15 - 7) * 2^e; mxfp4 the e2m1 code
+    h & 15 times its block scale, 2^(1 + e) for A and 2 for B."""
+    if form < 2:
+        return h % 31 - 15
+    if form == 2:
+        return (h % 15 - 7) << scale_bit
+    mag = _E2M1_TWICE[h & 7] << (scale_bit if is_a else 0)
+    return -mag if h & 8 else mag
 
 
-def _mfma_b(key: int, k: int, col: int) -> int:
-    """B[k][col] of one operand variant, -15..15."""
-    return _mix32(key ^ (k << 8) ^ col ^ 0x00B00000) % 31 - 15
+def _mfma_a(key: int, row: int, k: int, form: int = 0) -> int:
+    """A[row][k] of one operand variant, scale applied: bf16 and fp8 -15..15,
+    mxfp8 -14..14, mxfp4 -24..24."""
+    f = form << 24
+    h = _mix32(key ^ (row << 8) ^ k ^ 0x00A00000 ^ f)
+    e = _mix32(key ^ (row << 8) ^ (k // 32) ^ 0x00E00000 ^ f) & 1 if form >= 2 else 0
+    return _mfma_elem(form, h, e, True)
 
 
-def _mfma_product(seed: int, variant: int) -> List[List[int]]:
-    """The 64 x 64 product one step adds to a wave's tile: A (64 x 16) times
-    B (16 x 64) of `variant`, hashed from the low 32 bits of `seed`."""
+def _mfma_b(key: int, k: int, col: int, form: int = 0) -> int:
+    """B[k][col] of one operand variant, scale applied: bf16 and fp8 -15..15,
+    mxfp8 -14..14, mxfp4 -12..12."""
+    f = form << 24
+    h = _mix32(key ^ (k << 8) ^ col ^ 0x00B00000 ^ f)
+    e = _mix32(key ^ ((k // 32) << 8) ^ col ^ 0x00F00000 ^ f) & 1 if form == 2 else 0
+    return _mfma_elem(form, h, e, False)
+
+
+def _mfma_product(seed: int, variant: int, form: int = 0) -> List[List[int]]:
+    """The 64 x 64 product one step adds to a wave's tile: A (64 x K) times
+    B (K x 64) of `variant`, hashed from the low 32 bits of `seed`; K is the
+    form's. The probe lays A and B into the lanes by one rule, and every
+    element under the scale of its own block of 32 k, so which lane holds
+    which k does not enter the product."""
+    depth = MFMA_FORM_TABLE[MFMA_FORMS[form]]["k"]
     key = _mix32((seed & _M32) ^ (variant * 0x9E3779B1 & _M32))
-    a = [[_mfma_a(key, row, k) for k in range(16)] for row in range(64)]
-    b = [[_mfma_b(key, k, col) for col in range(64)] for k in range(16)]
-    cols = [[b[k][col] for k in range(16)] for col in range(64)]
+    a = [[_mfma_a(key, row, k, form) for k in range(depth)] for row in range(64)]
+    cols = [[_mfma_b(key, k, col, form) for k in range(depth)] for col in range(64)]
     return [[sum(x * y for x, y in zip(a[row], cols[col])) for col in range(64)]
             for row in range(64)]
 
 
-@functools.lru_cache(maxsize=8)
-def _mfma_lane_sums(seed32: int) -> Tuple[Tuple[int, ...], ...]:
+@functools.lru_cache(maxsize=16)
+def _mfma_lane_sums(seed32: int, form: int = 0) -> Tuple[Tuple[int, ...], ...]:
     """Per variant and lane, what one step adds to the lane's fold: lane r =
     lane & 31, h = lane >> 5 holds, in register reg of accumulator (m, n),
     row 32 m + (reg & 3) + 8 (reg >> 2) + 4 h of column 32 n + r, and weighs
-    it by 1 + reg + 16 (2 m + n)."""
+    it by 1 + reg + 16 (2 m + n). The same for every form."""
     out = []
     for variant in range(MFMA_VARIANTS):
-        p = _mfma_product(seed32, variant)
+        p = _mfma_product(seed32, variant, form)
         lanes = []
         for lane in range(64):
             r, h = lane & 31, lane >> 5
@@ -227,15 +268,29 @@ def _mfma_lane_sums(seed32: int) -> Tuple[Tuple[int, ...], ...]:
     return tuple(out)
 
 
-def mfma_checksum(workgroups: int, iters: int, seed: int) -> int:
+def _mfma_form_id(form: Optional[str]) -> int:
+    if form not in MFMA_FORMS:
+        raise ValueError(f"unknown mfma form {form!r}: one of " + ", ".join(MFMA_FORMS))
+    return MFMA_FORMS.index(form)
+
+
+def mfma_checksum(workgroups: int, iters: int, seed: int, form: str = "bf16") -> int:
     """What an mfma tenant's checksum must be. Wave w of the 4 * `workgroups`
     multiplies variant w % 16 of the operands, small integers hashed from the
     low 32 bits of `seed`, `iters` times into its 64 x 64 tile, and every
     lane folds its 64 accumulator registers, weighted, into one sum. The
     accumulators are exact and every fold is linear in the number of steps,
     so a lane's sum is iters times what one step adds; lane g = 64 w + lane
-    adds (g + 1) times its sum, modulo 2^64."""
-    sums = _mfma_lane_sums(int(seed) & _M32)
+    adds (g + 1) times its sum, modulo 2^64.
+
+    `form` is one of MFMA_FORMS (anything else raises ValueError). The forms
+    differ in the operands only: the hash takes the form's id, "fp8" holds
+    the same -15..15 as e4m3, "mxfp8" -7..7 as e4m3 and "mxfp4" e2m1 codes,
+    both at K = 64 under a scale of 2^e per row or column and block of 32 k
+    (mxfp8: e in {0, 1} on both sides; mxfp4: 1 + e for A, 1 for B), so that
+    every effective element is an integer and the product is taken from
+    integer matrices as for bf16."""
+    sums = _mfma_lane_sums(int(seed) & _M32, _mfma_form_id(form))
     waves = 4 * int(workgroups)
     total = 0
     for variant, lanes in enumerate(sums):
@@ -258,6 +313,7 @@ def _child_parser() -> argparse.ArgumentParser:
     p.add_argument("--bytes", type=int, default=0)
     p.add_argument("--passes", type=int, default=0)
     p.add_argument("--seed", type=int, default=1)
+    p.add_argument("--form", choices=MFMA_FORMS, default="bf16")
     return p
 
 
@@ -273,6 +329,10 @@ def child_main(argv: Optional[Sequence[str]] = None, stdin=None, stdout=None) ->
     probe = gpuprobe()
     window = {"kind": args.kind, "iters": args.iters, "bytes": args.bytes,
               "passes": args.passes, "seed": args.seed}
+    # The form is the mfma kind's; beside another kind only a form the probe
+    # would refuse is handed on, so that it does refuse it.
+    if args.kind in MATRIX_KINDS or args.form != MFMA_FORMS[0]:
+        window["form"] = args.form
     warm = probe.cu_tenant_run(args.device, None, launches=1, **window)
     if "skipped" in warm:
         print(f"cotenancy child: {warm}", file=sys.stderr)
@@ -365,8 +425,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
              kinds: Optional[Sequence[str]] = None, *, launches: int = 8,
              iters: int = 0, bytes: int = 0, passes: int = 0, seed: int = 1,
              timeout: float = 120.0,
-             spawn: Optional[Callable[[List[str], Dict[str, str]], Any]] = None
-             ) -> Dict[str, Any]:
+             spawn: Optional[Callable[[List[str], Dict[str, str]], Any]] = None,
+             form: Optional[str] = None) -> Dict[str, Any]:
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
     "fma" | "stream" | "cache" | "chase" | "mfma"} and may carry its own "launches", "iters",
@@ -374,6 +434,12 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     names the kinds instead. Every child warms up and says READY; only then
     are all told GO. Returns {"ok": True, "tenants": [the children's
     cu_tenant_run results]}.
+
+    `form` (one of MFMA_FORMS) is the instruction of every mfma tenant of
+    the call and leaves the others as they are; an mfma tenant may carry its
+    own "form" instead. An unknown form, or a "form" on a tenant of another
+    kind, raises ValueError before anything is started. A child is given
+    --form only when a form was named for it.
 
     Each child has `timeout` seconds from its start. The first child that
     times out, exits non-zero or prints no TENANT line ends the run: the
@@ -383,6 +449,19 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
         raise ValueError("run_pair takes one or two tenants")
     if kinds is not None and len(kinds) != len(tenants):
         raise ValueError("one kind per tenant")
+    if form is not None:
+        _mfma_form_id(form)
+    forms: List[Optional[str]] = []  # per tenant; None: the child is not told
+    for i, tenant in enumerate(tenants):
+        kind = kinds[i] if kinds is not None else tenant["kind"]
+        if kind not in MATRIX_KINDS:
+            if tenant.get("form") is not None:
+                raise ValueError(f"a {kind} tenant takes no form: {tenant['form']!r}")
+            forms.append(None)
+            continue
+        forms.append(form if tenant.get("form") is None else tenant["form"])
+        if forms[i] is not None:
+            _mfma_form_id(forms[i])
     spawn = _spawn if spawn is None else spawn
     root = str(Path(__file__).resolve().parents[2])
     children: List[_Child] = []
@@ -402,6 +481,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
                     "--bytes", str(tenant.get("bytes", bytes)),
                     "--passes", str(tenant.get("passes", passes)),
                     "--seed", str(seed)]
+            if forms[i] is not None:
+                argv += ["--form", forms[i]]
             try:
                 proc = spawn(argv, env)
             except OSError as exc:
@@ -461,8 +542,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                      passes: int = 0, seed: int = 1, timeout: float = 120.0,
                      spawn: Optional[Callable[..., Any]] = None,
                      expected_checksum: Optional[Callable[[int, int], int]] = None,
-                     windows: Optional[Mapping[str, Mapping[str, int]]] = None
-                     ) -> Dict[str, Any]:
+                     windows: Optional[Mapping[str, Mapping[str, int]]] = None,
+                     form: Optional[str] = None) -> Dict[str, Any]:
     """Each of two tenants' ({"mask": int}) rate alone and next to the other.
 
     First one solo run per tenant and kind that `pairs` uses, then the pairs
@@ -499,6 +580,14 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     cycle_ratio the part that it does not: a tenant slowed only by the
     neighbour's effect on the clock has cycle_ratio 1.
 
+    `form` (one of MFMA_FORMS, anything else raises ValueError) is the
+    instruction the mfma tenants issue, alone and in every pair; a tenant
+    ({"mask": int, "form": str}) may name its own instead, for a bf16 tenant
+    beside an mxfp4 one. The other kinds are not touched by it. A tenant's
+    checksum is held against mfma_checksum() of its own form, and its mfma
+    entries, solo and in a pair, add "form". With no form named anywhere the
+    children are started as before, run bf16, and no entry has "form".
+
     ok says that the measurement is valid (every child exited 0, every
     stream and cache checksum equals the pattern's, every chase and mfma
     checksum the closed form's, overlap was reached), not that the
@@ -515,6 +604,10 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     for kind, w in windows.items():
         if kind not in ALL_KINDS or any(k not in WINDOW_KEYS for k in w):
             raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
+    forms = [form if t.get("form") is None else t["form"] for t in tenants]
+    for f in forms:
+        if f is not None:
+            _mfma_form_id(f)
     expected_checksum = expected_checksum or _pattern_checksum
     window = {"iters": iters, "bytes": bytes, "passes": passes, "seed": seed,
               "timeout": timeout, "spawn": spawn}
@@ -527,8 +620,15 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         for k, v in more.items():
             report.setdefault(k, v)
 
-    def sound(result: Mapping[str, Any]) -> Optional[str]:
-        """Why a child's result cannot be used, or None."""
+    def asked(i: int, kind: str) -> Dict[str, Any]:
+        """What tenant i is started with as `kind`, beyond mask and launches."""
+        more: Dict[str, Any] = dict(windows.get(kind, {}))
+        if kind in MATRIX_KINDS and forms[i] is not None:
+            more["form"] = forms[i]
+        return more
+
+    def sound(result: Mapping[str, Any], i: int) -> Optional[str]:
+        """Why the result of tenant i's child cannot be used, or None."""
         if "skipped" in result:
             return "insufficient-memory"
         if result["kind"] in READING_KINDS:
@@ -543,7 +643,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 return "bad-checksum"
         if result["kind"] in MATRIX_KINDS:
             if int(result["checksum"]) != mfma_checksum(
-                    result["workgroups"], result["iters"], seed):
+                    result["workgroups"], result["iters"], seed,
+                    forms[i] or MFMA_FORMS[0]):
                 return "bad-checksum"
         return None
 
@@ -552,13 +653,13 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
             if not any(pair[i] == kind for pair in pairs):
                 continue
             run = run_pair(card, [{"mask": tenant["mask"], "kind": kind,
-                                   **windows.get(kind, {})}],
+                                   **asked(i, kind)}],
                            launches=launches, **window)
             if not run["ok"]:
                 flaw(run["reason"], detail=run["detail"])
                 return report
             result = run["tenants"][0]
-            why = sound(result)
+            why = sound(result, i)
             if why == "insufficient-memory":
                 flaw(why)
                 return report
@@ -573,13 +674,15 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 report["solo"][i][kind]["ns_per_hop"] = result["ns_per_hop"]
             if kind in MATRIX_KINDS:
                 report["solo"][i][kind]["clock_ghz"] = result["clock_ghz"]
+                if forms[i] is not None:
+                    report["solo"][i][kind]["form"] = forms[i]
 
     for pair in pairs:
         name = "/".join(pair)
         counts = _balanced(launches, [report["solo"][i][pair[i]]["seconds"]
                                       for i in range(2)])
         run = run_pair(card, [{"mask": tenants[i]["mask"], "kind": pair[i],
-                               "launches": counts[i], **windows.get(pair[i], {})}
+                               "launches": counts[i], **asked(i, pair[i])}
                               for i in range(2)],
                        launches=launches, **window)
         if not run["ok"]:
@@ -589,7 +692,7 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         results = run["tenants"]
         entry: Dict[str, Any] = {"ok": True, "tenants": []}
         for i in range(2):
-            why = sound(results[i])
+            why = sound(results[i], i)
             if why == "insufficient-memory":
                 flaw(why)
                 report["pairs"][name] = {"ok": False, "reason": why}
@@ -603,6 +706,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 "contended_launches": len(rates), "launches": len(mine),
                 "solo_launches": labels.count("solo"),
                 "mixed_launches": labels.count("mixed")}
+            if pair[i] in MATRIX_KINDS and forms[i] is not None:
+                t["form"] = forms[i]
             if len(rates) < MIN_CONTENDED:
                 why = why or "no-overlap"
             else:

@@ -23,7 +23,8 @@ processes under disjoint masks, each one's rate alone and next to the other.
 --co-tenancy-cache does the same for a tenant whose working set fits a cache,
 --co-tenancy-chase for a tenant bound by the latency of dependent loads,
 --co-tenancy-mfma for a tenant on the matrix cores, whose clock is the
-chip's and follows no mask.
+chip's and follows no mask; --co-tenancy-mfma-form runs that tenant with the
+FP8 or block-scaled MX instructions in place of the bf16 one.
 """
 from __future__ import annotations
 
@@ -57,6 +58,18 @@ def mib_list_arg(text: str):
         raise argparse.ArgumentTypeError(
             f"expected sizes of 1..1024 MiB as M[,M...], got {text!r}")
     return sizes
+
+
+def mfma_forms_arg(text: str):
+    """"FORM[,FORM...]": forms of the mfma tenant's instruction."""
+    from elastic_gpu_scheduler_amd.agent.cotenancy import MFMA_FORMS
+
+    forms = tuple(text.split(","))
+    if not all(f in MFMA_FORMS for f in forms):
+        raise argparse.ArgumentTypeError(
+            f"expected forms out of {', '.join(MFMA_FORMS)} as FORM[,FORM...], "
+            f"got {text!r}")
+    return forms
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -119,6 +132,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "clock explains (clock_ratio) and the part that it "
                         "does not (cycle_ratio); not together with "
                         "--co-tenancy-cache or --co-tenancy-chase")
+    p.add_argument("--co-tenancy-mfma-form", type=mfma_forms_arg, default=None,
+                   metavar="FORM[,FORM...]",
+                   help="with --co-tenancy-mfma: the instruction the MFMA "
+                        "tenants issue, out of bf16, fp8 (e4m3, the bf16 "
+                        "rate), mxfp8 and mxfp4 (block-scaled, 2 x and 4 x "
+                        "the bf16 work per clock); one report per card and "
+                        "form, one after another")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -165,11 +185,23 @@ def main(argv=None) -> int:
                   file=sys.stderr)
             return 2
 
+    if args.co_tenancy_mfma_form is not None and not args.co_tenancy_mfma:
+        print("--co-tenancy-mfma-form needs --co-tenancy-mfma", file=sys.stderr)
+        return 2
+
     if args.co_tenancy_mfma:
         from elastic_gpu_scheduler_amd.agent.cotenancy import MFMA_PAIRS
 
         agent = NodeAgent(args.node or "local", client=None,
                           prefer_source=args.source)
+        if args.co_tenancy_mfma_form is not None:
+            # One card and one form after another: never more than two
+            # children at once.
+            print(json.dumps({card: {form: agent.verify_isolation(
+                card, args.co_tenancy, pairs=MFMA_PAIRS, form=form)
+                for form in args.co_tenancy_mfma_form}
+                for card in sorted(agent.mask_layouts())}, indent=2))
+            return 0
         # One card after another: never more than two children at once.
         print(json.dumps({card: agent.verify_isolation(
             card, args.co_tenancy, pairs=MFMA_PAIRS)

@@ -5,7 +5,8 @@
 //     stream over one large allocation ("stream"), repeated reads of a
 //     working set that every workgroup keeps to itself ("cache"), a walk
 //     along a chain of dependent loads, one in flight per wave ("chase"), or
-//     bf16 MFMAs issued back to back on operands held in registers ("mfma"),
+//     MFMAs (bf16, or the fp8, mxfp8 or mxfp4 form) issued back to back on
+//     operands held in registers ("mfma"),
 //     each launch stamped with the device's constant-rate wall clock. The
 //     clock is the card's, not the
 //     process's, so two separate processes can lay their launches side by
@@ -51,9 +52,8 @@ constexpr uint64_t kNodeWords = kNodeBytes / 8;
 constexpr int kMaxChaseIters = 1 << 22;
 constexpr int kMfmaGroupsPerCu = 8;  // "mfma": one wave per SIMD already fills the pipe
 constexpr int kMfmaVariants = 16;    // operand sets; wave w uses w % 16
-constexpr int kMfmaChunk = 2048;     // steps between two folds of the accumulators
 constexpr int kMaxMfmaIters = 1 << 20;
-constexpr double kMfmaFlops = 2.0 * 32 * 32 * 16;  // one 32x32x16 MFMA
+constexpr double kMfmaFlopsPerK = 2.0 * 32 * 32;  // one 32x32xK MFMA, per unit of K
 constexpr uint64_t kGiB = 1ULL << 30;
 constexpr uint64_t kMiB = 1ULL << 20;
 
@@ -270,6 +270,8 @@ uint64_t chase_stride(uint64_t nodes) {
 
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using short8 = __attribute__((ext_vector_type(8))) short;
+using int4v = __attribute__((ext_vector_type(4))) int;
+using int8v = __attribute__((ext_vector_type(8))) int;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 __device__ inline uint32_t mix32(uint32_t x) {
@@ -281,14 +283,45 @@ __device__ inline uint32_t mix32(uint32_t x) {
   return x;
 }
 
-// A[row][k] and B[k][col] of one operand variant, both in -15..15. Hashed, so
-// neither is symmetric in its two indices. agent/cotenancy.py states the same
-// rule on its own.
-__device__ inline int mfma_a_elem(uint32_t key, uint32_t row, uint32_t k) {
-  return static_cast<int>(mix32(key ^ (row << 8) ^ k ^ 0x00A00000u) % 31u) - 15;
+// The instruction an mfma tenant issues. The id enters the operand hashes,
+// so no two forms multiply the same matrices.
+enum MfmaFormId : int { kBf16 = 0, kFp8 = 1, kMxfp8 = 2, kMxfp4 = 3 };
+constexpr int kMfmaForms = 4;
+
+// Per form: the K of one MFMA, the steps between two folds of the
+// accumulators (the largest partial sum of a chunk stays below 2^23, see the
+// kernel) and the steps of a default launch, about as long for every form.
+// agent/cotenancy.py keeps the same table.
+struct MfmaFormInfo {
+  const char* name;
+  int k, chunk, default_iters;
+};
+constexpr MfmaFormInfo kMfmaFormTable[kMfmaForms] = {
+    {"bf16", 16, 2048, 32768},
+    {"fp8", 16, 2048, 32768},
+    {"mxfp8", 64, 512, 16384},
+    {"mxfp4", 64, 256, 32768},
+};
+
+// The hashes behind A[row][k] and B[k][col] of one operand variant and, for
+// the block-scaled forms, behind the scale of a row's or column's block of 32
+// k. Hashed, so nothing is symmetric in its two indices; for bf16 (F = 0) the
+// form's bits vanish. agent/cotenancy.py states the same rules on its own.
+template <int F>
+__device__ inline uint32_t mfma_a_hash(uint32_t key, uint32_t row, uint32_t k) {
+  return mix32(key ^ (row << 8) ^ k ^ 0x00A00000u ^ (static_cast<uint32_t>(F) << 24));
 }
-__device__ inline int mfma_b_elem(uint32_t key, uint32_t k, uint32_t col) {
-  return static_cast<int>(mix32(key ^ (k << 8) ^ col ^ 0x00B00000u) % 31u) - 15;
+template <int F>
+__device__ inline uint32_t mfma_b_hash(uint32_t key, uint32_t k, uint32_t col) {
+  return mix32(key ^ (k << 8) ^ col ^ 0x00B00000u ^ (static_cast<uint32_t>(F) << 24));
+}
+template <int F>
+__device__ inline uint32_t mfma_a_scale_bit(uint32_t key, uint32_t row, uint32_t blk) {
+  return mix32(key ^ (row << 8) ^ blk ^ 0x00E00000u ^ (static_cast<uint32_t>(F) << 24)) & 1u;
+}
+template <int F>
+__device__ inline uint32_t mfma_b_scale_bit(uint32_t key, uint32_t blk, uint32_t col) {
+  return mix32(key ^ (blk << 8) ^ col ^ 0x00F00000u ^ (static_cast<uint32_t>(F) << 24)) & 1u;
 }
 
 // Small integers are exact in bf16: the bf16 is the float's upper half.
@@ -296,50 +329,201 @@ __device__ inline short to_bf16_bits(int v) {
   return static_cast<short>(__float_as_uint(static_cast<float>(v)) >> 16);
 }
 
+// -15..15 as OCP e4m3fn (bias 7, three mantissa bits): 1 is 0x38, 15 is 0x57.
+__device__ inline uint32_t to_e4m3_bits(int v) {
+  if (v == 0) return 0u;
+  const uint32_t mag = static_cast<uint32_t>(v < 0 ? -v : v);
+  const uint32_t e = 31u - static_cast<uint32_t>(__builtin_clz(mag));  // 0..3
+  return (v < 0 ? 0x80u : 0u) | ((e + 7u) << 3) | ((mag << (3u - e)) & 7u);
+}
+
+// One wave's operand fragments of a form: two of A, two of B and, for the
+// block-scaled forms, the E8M0 scale (byte 0: 2^(byte - 127)) that goes with
+// each. Lane r = lane & 31, h = lane >> 5 of fragment t holds row or column
+// 32t + r, element j in the j-th slot of the lane's registers from the low
+// end: a bf16 per 16 bits, an e4m3 per byte, an e2m1 per nibble. For bf16
+// and fp8 that is k = 8h + j, j = 0..7, and for mxfp4 k = 32h + j, j = 0..31:
+// the lane's four dwords are block h of 32 k. For mxfp8 a lane's eight dwords
+// are half of each block, dwords 0..3 k = 16h + j and dwords 4..7 k = 32 +
+// 16h + (j - 16): the instruction scales a lane's low four dwords by the
+// scale register of lane r and its high four by that of lane r + 32 (found
+// on the card with exact data: with k = 32h + j every product came out as if
+// scaled that way). In both block-scaled forms the scale register of lane r +
+// 32h holds the scale of block h. A and B follow the same rule, so whatever
+// order the instruction gives the k inside a block, it pairs equal k.
+//   bf16, fp8: h % 31 - 15.
+//   mxfp8: h % 15 - 7, scale byte 127 + e on both sides: |element| <= 14.
+//   mxfp4: the code h & 15 as it is, +-(0, 0.5, 1, 1.5, 2, 3, 4, 6)[code & 7],
+//          negative with code & 8; A's scale byte 128 + e, B's 128: every
+//          effective element is an integer, |A| <= 24 and |B| <= 12.
+template <int F>
+struct MfmaFrags;
+
+template <>
+struct MfmaFrags<kBf16> {
+  bf16x8 a[2], b[2];
+  __device__ void build(uint32_t key, uint32_t r, uint32_t h) {
+#pragma unroll
+    for (uint32_t t = 0; t < 2; ++t) {
+      short8 af, bf;
+#pragma unroll
+      for (uint32_t j = 0; j < 8; ++j) {
+        af[j] = to_bf16_bits(
+            static_cast<int>(mfma_a_hash<kBf16>(key, 32 * t + r, 8 * h + j) % 31u) - 15);
+        bf[j] = to_bf16_bits(
+            static_cast<int>(mfma_b_hash<kBf16>(key, 8 * h + j, 32 * t + r) % 31u) - 15);
+      }
+      a[t] = __builtin_bit_cast(bf16x8, af);
+      b[t] = __builtin_bit_cast(bf16x8, bf);
+    }
+  }
+  __device__ void pin() {
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
+  }
+  __device__ f32x16 mfma(int m, int n, f32x16 c) const {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m], b[n], c, 0, 0, 0);
+  }
+};
+
+template <>
+struct MfmaFrags<kFp8> {
+  long a[2], b[2];
+  __device__ void build(uint32_t key, uint32_t r, uint32_t h) {
+#pragma unroll
+    for (uint32_t t = 0; t < 2; ++t) {
+      uint64_t af = 0, bf = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < 8; ++j) {
+        af |= static_cast<uint64_t>(to_e4m3_bits(
+                  static_cast<int>(mfma_a_hash<kFp8>(key, 32 * t + r, 8 * h + j) % 31u) - 15))
+              << (8 * j);
+        bf |= static_cast<uint64_t>(to_e4m3_bits(
+                  static_cast<int>(mfma_b_hash<kFp8>(key, 8 * h + j, 32 * t + r) % 31u) - 15))
+              << (8 * j);
+      }
+      a[t] = static_cast<long>(af);
+      b[t] = static_cast<long>(bf);
+    }
+  }
+  __device__ void pin() {
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
+  }
+  __device__ f32x16 mfma(int m, int n, f32x16 c) const {
+    return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a[m], b[n], c, 0, 0, 0);
+  }
+};
+
+template <>
+struct MfmaFrags<kMxfp8> {
+  int8v a[2], b[2];
+  int sa[2], sb[2];
+  __device__ void build(uint32_t key, uint32_t r, uint32_t h) {
+#pragma unroll
+    for (uint32_t t = 0; t < 2; ++t) {
+#pragma unroll
+      for (uint32_t d = 0; d < 8; ++d) {
+        uint32_t aw = 0, bw = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {
+          const uint32_t k = 32 * (d >> 2) + 16 * h + 4 * (d & 3) + q;
+          aw |= to_e4m3_bits(
+                    static_cast<int>(mfma_a_hash<kMxfp8>(key, 32 * t + r, k) % 15u) - 7)
+                << (8 * q);
+          bw |= to_e4m3_bits(
+                    static_cast<int>(mfma_b_hash<kMxfp8>(key, k, 32 * t + r) % 15u) - 7)
+                << (8 * q);
+        }
+        a[t][d] = static_cast<int>(aw);
+        b[t][d] = static_cast<int>(bw);
+      }
+      sa[t] = static_cast<int>(127u + mfma_a_scale_bit<kMxfp8>(key, 32 * t + r, h));
+      sb[t] = static_cast<int>(127u + mfma_b_scale_bit<kMxfp8>(key, h, 32 * t + r));
+    }
+  }
+  __device__ void pin() {
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
+    asm volatile("" : "+v"(sa[0]), "+v"(sa[1]), "+v"(sb[0]), "+v"(sb[1]));
+  }
+  __device__ f32x16 mfma(int m, int n, f32x16 c) const {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[m], b[n], c, 0, 0, 0, sa[m], 0,
+                                                           sb[n]);
+  }
+};
+
+template <>
+struct MfmaFrags<kMxfp4> {
+  int4v a[2], b[2];  // the low four of the instruction's eight dwords
+  int sa[2], sb[2];
+  __device__ void build(uint32_t key, uint32_t r, uint32_t h) {
+#pragma unroll
+    for (uint32_t t = 0; t < 2; ++t) {
+#pragma unroll
+      for (uint32_t d = 0; d < 4; ++d) {
+        uint32_t aw = 0, bw = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 8; ++q) {
+          const uint32_t k = 32 * h + 8 * d + q;
+          aw |= (mfma_a_hash<kMxfp4>(key, 32 * t + r, k) & 15u) << (4 * q);
+          bw |= (mfma_b_hash<kMxfp4>(key, k, 32 * t + r) & 15u) << (4 * q);
+        }
+        a[t][d] = static_cast<int>(aw);
+        b[t][d] = static_cast<int>(bw);
+      }
+      sa[t] = static_cast<int>(128u + mfma_a_scale_bit<kMxfp4>(key, 32 * t + r, h));
+      sb[t] = 128;
+    }
+  }
+  __device__ void pin() {
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
+    asm volatile("" : "+v"(sa[0]), "+v"(sa[1]), "+v"(sb[0]), "+v"(sb[1]));
+  }
+  __device__ static int8v widen(int4v v) {
+    return int8v{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
+  }
+  __device__ f32x16 mfma(int m, int n, f32x16 c) const {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[m]), widen(b[n]), c, 4, 4,
+                                                           0, sa[m], 0, sb[n]);
+  }
+};
+
 // Every wave owns a 64x64 output tile, 2 x 2 accumulators of 32x32, and keeps
-// two A fragments (rows 32m + r) and two B fragments (columns 32n + r) of K =
-// 16 in registers: lane r = lane & 31, h = lane >> 5 holds A[r][8h + j] and
-// B[8h + j][r], and output register reg is row (reg & 3) + 8 * (reg >> 2) + 4h
-// of column r. The fragments are built once, before the start stamp, from
-// variant (global wave) % 16 of the hashes above. One step is the four MFMAs
-// acc[m][n] += A_m x B_n; `iters` steps run in chunks of at most kMfmaChunk.
-// A chunk starts from zero accumulators and ends with every lane folding its
-// 64 registers into a 64-bit sum, each weighted by 1 + reg + 16 * (2m + n).
-// |A x B| <= 16 * 225 = 3600 per step and 2048 * 3600 < 2^23, so every partial
-// sum is exact in f32, its conversion to int is exact, and the fold is linear
-// in the number of steps. Nothing is read from memory between the stamps.
+// two A fragments (rows 32m + r) and two B fragments (columns 32n + r) of the
+// form's K in registers (MfmaFrags above); output register reg is row (reg &
+// 3) + 8 * (reg >> 2) + 4h of column r, for every form. The fragments are
+// built once, before the start stamp, from variant (global wave) % 16 of the
+// hashes above. One step is the four MFMAs acc[m][n] += A_m x B_n; `iters`
+// steps run in chunks of at most the form's chunk. A chunk starts from zero
+// accumulators and ends with every lane folding its 64 registers into a
+// 64-bit sum, each weighted by 1 + reg + 16 * (2m + n). Per step |A x B| <=
+// 16 * 15 * 15 = 3600 (bf16, fp8), 64 * 14 * 14 = 12544 (mxfp8), 64 * 24 * 12
+// = 18432 (mxfp4), and 2048 * 3600, 512 * 12544 and 256 * 18432 are all below
+// 2^23, so every partial sum is exact in f32, its conversion to int is exact,
+// and the fold is linear in the number of steps. Nothing is read from memory
+// between the stamps.
 //
 // clk is the launch's {sum of shader cycles, sum of wall ticks}: thread 0 of
 // every workgroup reads s_memtime next to each end of its wall-clock interval
 // and adds both differences. cycles / ticks x tick_hz is the shader clock the
 // launch ran at, averaged over its workgroups.
+template <int F>
 __global__ void __launch_bounds__(kBlock)
 tenant_mfma_kernel(uint32_t seed32, int iters, unsigned long long* __restrict__ out,
                    unsigned long long* __restrict__ rec,
                    unsigned long long* __restrict__ clk) {
+  constexpr int kChunk = kMfmaFormTable[F].chunk;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t r = lane & 31u, h = lane >> 5;
   const uint32_t w = blockIdx.x * kWavesPerGroup + threadIdx.x / 64;
   const uint32_t key = mix32(seed32 ^ ((w % kMfmaVariants) * 0x9E3779B1u));
-  bf16x8 a[2], b[2];
-#pragma unroll
-  for (uint32_t t = 0; t < 2; ++t) {
-    short8 af, bf;
-#pragma unroll
-    for (uint32_t j = 0; j < 8; ++j) {
-      af[j] = to_bf16_bits(mfma_a_elem(key, 32 * t + r, 8 * h + j));
-      bf[j] = to_bf16_bits(mfma_b_elem(key, 8 * h + j, 32 * t + r));
-    }
-    a[t] = __builtin_bit_cast(bf16x8, af);
-    b[t] = __builtin_bit_cast(bf16x8, bf);
-  }
+  MfmaFrags<F> frags;
+  frags.build(key, r, h);
   // The fragments are in their registers before either clock is read.
-  asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
+  frags.pin();
   const unsigned long long c0 = __builtin_amdgcn_s_memtime();
   const unsigned long long t0 = stamp_start();
   uint64_t fold = 0;
-  for (int done = 0; done < iters; done += kMfmaChunk) {
-    const int steps = min(iters - done, kMfmaChunk);
+  for (int done = 0; done < iters; done += kChunk) {
+    const int steps = min(iters - done, kChunk);
     f32x16 acc[2][2];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -348,8 +532,7 @@ tenant_mfma_kernel(uint32_t seed32, int iters, unsigned long long* __restrict__ 
     for (int i = 0; i < steps; ++i) {
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        acc[t >> 1][t & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            a[t >> 1], b[t & 1], acc[t >> 1][t & 1], 0, 0, 0);
+        acc[t >> 1][t & 1] = frags.mfma(t >> 1, t & 1, acc[t >> 1][t & 1]);
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -384,6 +567,7 @@ struct TenantResult {
   bool skipped = false;
   uint64_t free_bytes = 0;
   Kind kind = Kind::kFma;
+  int form = kBf16;  // mfma only
   MaskWords applied;
   double tick_hz = 0.0;
   int workgroups = 0;
@@ -400,7 +584,7 @@ struct TenantResult {
 };
 
 TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int launches,
-                        int iters, uint64_t bytes, int passes, uint64_t seed) {
+                        int iters, uint64_t bytes, int passes, uint64_t seed, int form) {
   require_device(device);
   const int cus = gpuprobe::device_cus(device);
   const MaskWords mask =
@@ -429,10 +613,12 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     r.iters = std::min(iters, 1 << 18);
     r.work_per_launch = 2.0 * kFmaChains * static_cast<double>(lanes) * r.iters;
   } else if (mfma) {
-    if (iters <= 0) iters = 32768;
+    r.form = form;
+    if (iters <= 0) iters = kMfmaFormTable[form].default_iters;
     r.iters = std::min(iters, kMaxMfmaIters);  // steps of four MFMAs per wave and launch
     r.work_per_launch = static_cast<double>(grid) * kWavesPerGroup *
-                        static_cast<double>(r.iters) * 4.0 * kMfmaFlops;
+                        static_cast<double>(r.iters) * 4.0 * kMfmaFlopsPerK *
+                        kMfmaFormTable[form].k;
   } else {
     const bool cache = kind == Kind::kCache;
     if (chase) {
@@ -498,13 +684,17 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
   {
     StreamGuard g;
     gpuprobe::open_stream(g, mask, r.applied);
+    const auto mfma_kernel = form == kFp8     ? tenant_mfma_kernel<kFp8>
+                             : form == kMxfp8 ? tenant_mfma_kernel<kMxfp8>
+                             : form == kMxfp4 ? tenant_mfma_kernel<kMxfp4>
+                                              : tenant_mfma_kernel<kBf16>;
     auto launch = [&](int slot) {
       unsigned long long* rec = recs.as<unsigned long long>() + 2 * slot;
       if (kind == Kind::kFma)
         hipLaunchKernelGGL(tenant_fma_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                            out.as<float>(), r.iters, 0.999f, 0.001f, rec);
       else if (mfma)
-        hipLaunchKernelGGL(tenant_mfma_kernel, dim3(grid), dim3(kBlock), 0, g.s,
+        hipLaunchKernelGGL(mfma_kernel, dim3(grid), dim3(kBlock), 0, g.s,
                            static_cast<uint32_t>(seed), r.iters,
                            out.as<unsigned long long>(), rec,
                            clks.as<unsigned long long>() + 2 * slot);
@@ -610,7 +800,7 @@ void register_cotenant(py::module_& m) {
   m.def(
       "cu_tenant_run",
       [](int device, py::object mask, const std::string& kind, int launches, int iters,
-         uint64_t bytes, int passes, uint64_t seed) {
+         uint64_t bytes, int passes, uint64_t seed, const std::string& form) {
         const MaskWords words = gpuprobe::mask_from_python(mask);
         Kind k;
         if (kind == "fma")
@@ -627,10 +817,20 @@ void register_cotenant(py::module_& m) {
           throw py::value_error(
               "cu_tenant_run: kind must be \"fma\", \"stream\", \"cache\", "
               "\"chase\" or \"mfma\"");
+        int f = 0;
+        while (f < kMfmaForms && form != kMfmaFormTable[f].name) ++f;
+        if (f == kMfmaForms)
+          throw py::value_error(
+              "cu_tenant_run: form must be \"bf16\", \"fp8\", \"mxfp8\" or \"mxfp4\"");
+        if (f != kBf16 && k != Kind::kMfma)
+          throw py::value_error(
+              "cu_tenant_run: form \"" + form + "\" needs kind \"mfma\"; of the forms "
+              "\"bf16\", \"fp8\", \"mxfp8\" and \"mxfp4\" every other kind takes only "
+              "\"bf16\"");
         TenantResult r;
         {
           py::gil_scoped_release release;
-          r = run_tenant(device, words, k, launches, iters, bytes, passes, seed);
+          r = run_tenant(device, words, k, launches, iters, bytes, passes, seed, f);
         }
         py::dict d;
         if (r.skipped) {
@@ -646,6 +846,7 @@ void register_cotenant(py::module_& m) {
         if (k == Kind::kFma) {
           d["iters"] = r.iters;
         } else if (k == Kind::kMfma) {
+          d["form"] = kMfmaFormTable[r.form].name;
           d["iters"] = r.iters;
           d["checksum"] = r.checksum;
         } else if (k == Kind::kChase) {
@@ -684,7 +885,7 @@ void register_cotenant(py::module_& m) {
       },
       py::arg("device") = 0, py::arg("mask") = py::none(), py::arg("kind") = "fma",
       py::arg("launches") = 8, py::arg("iters") = 0, py::arg("bytes") = 0,
-      py::arg("passes") = 0, py::arg("seed") = 1,
+      py::arg("passes") = 0, py::arg("seed") = 1, py::arg("form") = "bf16",
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
@@ -774,10 +975,42 @@ void register_cotenant(py::module_& m) {
       "(all-zero operands have been seen to run 19 % faster than random "
       "ones at equal cycles), which is why the result reports the clock it "
       "saw and not only the rate.\n\n"
+      "mfma, `form`: the instruction, \"bf16\" (the default, everything above), "
+      "\"fp8\", \"mxfp8\" or \"mxfp4\"; anything else, or a form other than "
+      "\"bf16\" with a kind other than \"mfma\", raises ValueError before the "
+      "device is touched. Tile, fragments in registers, steps, fold, clocks "
+      "and grid are the same for every form; the result adds form, and "
+      "work_per_launch = waves * iters * 4 * the form's flop per MFMA. The "
+      "form's id f (0..3 in the order above) enters the hashes: A[row][k] "
+      "from mix32(key ^ row << 8 ^ k ^ 0xA00000 ^ f << 24), B[k][col] from "
+      "mix32(key ^ k << 8 ^ col ^ 0xB00000 ^ f << 24). fp8: "
+      "v_mfma_f32_32x32x16_fp8_fp8 on OCP e4m3fn operands, K = 16, 32768 "
+      "flop, the same hash % 31 - 15, chunks of 2048, default 32768 steps. "
+      "mxfp8: v_mfma_scale_f32_32x32x64_f8f6f4 on e4m3 operands, K = 64, "
+      "131072 flop, hash % 15 - 7, chunks of 512, default 16384 steps (a "
+      "step takes twice the cycles). mxfp4: the same instruction on e2m1 "
+      "operands, K = 64, 131072 flop, the code hash & 15 stored as it is (+-"
+      "(0, 0.5, 1, 1.5, 2, 3, 4, 6)[code & 7], negative with code & 8), "
+      "chunks of 256, default 32768 steps. Both block-scaled forms give "
+      "every row of A and column of B one E8M0 scale (byte s: 2^(s - 127)) "
+      "per block of 32 k, from the bits eA = mix32(key ^ row << 8 ^ blk ^ "
+      "0xE00000 ^ f << 24) & 1 and eB = mix32(key ^ blk << 8 ^ col ^ 0xF00000 "
+      "^ f << 24) & 1: mxfp8 byte 127 + e on both sides (|element| <= 14), "
+      "mxfp4 byte 128 + eA for A (|A| <= 24) and 128 for B (|B| <= 12), so "
+      "every effective element is an integer. Lane r + 32 h of fragment t "
+      "holds row or column 32 t + r, element j in the j-th slot from the low "
+      "end, at k = 8 h + j (bf16, fp8), k = 32 h + j (mxfp4: the lane's four "
+      "dwords are block h) or k = 32 (j // 16) + 16 h + j % 16 (mxfp8: the "
+      "lane's low four dwords are half of block 0 and its high four half of "
+      "block 1, which is how the instruction applies the scales); the scale "
+      "register of lane r + 32 h holds the scale of block h; both sides "
+      "alike. A chunk's partial "
+      "sums stay below 2048 * 3600, 512 * 12544 and 256 * 18432, all below "
+      "2^23, so mfma_checksum(..., form) is exact for every form.\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
-      "{kind, applied_mask, tick_hz, workgroups, iters | bytes, passes, checksum, "
+      "{kind, [form,] applied_mask, tick_hz, workgroups, iters | bytes, passes, checksum, "
       "[bytes_per_cu,] work_per_launch: flops, bytes or hops, launches: [{t0, t1, "
       "seconds: (t1 - t0) "
       "/ tick_hz, event_seconds, rate[, cycles, ticks, clock_ghz]}], rate[, "
