@@ -438,7 +438,7 @@ class NodeAgent:
         containers are wired: each tenant's FMA and HBM-stream rate alone and
         while the other runs (cotenancy.isolation_report, to which `window`
         is passed: pairs, launches, iters, bytes, passes, timeout, windows,
-        form).
+        form, operands).
         Returns that report plus "tenants": [{core, mask, cus}].
 
         pairs=cotenancy.CACHE_PAIRS brings in the third kind, a tenant that
@@ -458,7 +458,11 @@ class NodeAgent:
         names the instruction the mfma tenants issue in place of the bf16
         one; their entries then add "form". For two tenants of different
         forms, such as bf16 beside mxfp4, call cotenancy.isolation_report
-        with a "form" in each tenant.
+        with a "form" in each tenant. operands= (one of
+        cotenancy.MFMA_OPERANDS: "registers", "lds") says where the mfma
+        tenants take their operands from: "lds" makes them re-read every
+        step's operands from LDS, as a GEMM does, in place of keeping them
+        in registers; their entries then add "operands".
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched

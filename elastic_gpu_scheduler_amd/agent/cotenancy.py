@@ -34,7 +34,11 @@ saw, and split a tenant's ratio into the part the clock explains and the
 part it does not. Its oracle, mfma_checksum(), is here too, in integers only.
 The kind has a form (MFMA_FORMS): the bf16 instruction by default, or its fp8
 twin, or the block-scaled MXFP8 and MXFP4 ones that inference tenants run,
-2 x and 4 x the bf16 work per clock through the same pipe.
+2 x and 4 x the bf16 work per clock through the same pipe. And its operands
+come from one of two places (MFMA_OPERANDS): "registers", where they stay
+for the whole launch, or "lds", re-read from the workgroup's LDS before every
+step as a GEMM re-reads its own, the slot rotating with the step. The LDS is
+a CU's, so a mask isolates it fully; the clock it helps to pull down is not.
 
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
@@ -188,6 +192,14 @@ MFMA_FORM_TABLE: Dict[str, Dict[str, int]] = {
     "mxfp8": {"k": 64, "flop": 131072, "chunk": 512, "iters": 16384},
     "mxfp4": {"k": 64, "flop": 131072, "chunk": 256, "iters": 32768},
 }
+# Where an mfma tenant's operands come from: kept in registers for the whole
+# launch, or re-read from LDS before every step.
+MFMA_OPERANDS = ("registers", "lds")
+# Operands from LDS, as in csrc/gpuprobe/cotenant.hip: a workgroup's image is
+# one slot per wave, and a slot is the bytes a wave reads per step.
+MFMA_LDS_SLOTS = 4
+MFMA_LDS_STEP_BYTES: Dict[str, int] = {
+    "bf16": 4096, "fp8": 2048, "mxfp8": 9216, "mxfp4": 5120}
 # Twice the magnitude of e2m1 code & 7 (0, 0.5, 1, 1.5, 2, 3, 4, 6): the mxfp4
 # scales are 2 or 4, so every effective element is an integer.
 _E2M1_TWICE = (0, 1, 2, 3, 4, 6, 8, 12)
@@ -274,7 +286,15 @@ def _mfma_form_id(form: Optional[str]) -> int:
     return MFMA_FORMS.index(form)
 
 
-def mfma_checksum(workgroups: int, iters: int, seed: int, form: str = "bf16") -> int:
+def _mfma_operands(operands: Optional[str]) -> str:
+    if operands not in MFMA_OPERANDS:
+        raise ValueError(f"unknown mfma operands {operands!r}: one of "
+                         + ", ".join(MFMA_OPERANDS))
+    return operands
+
+
+def mfma_checksum(workgroups: int, iters: int, seed: int, form: str = "bf16",
+                  operands: str = "registers") -> int:
     """What an mfma tenant's checksum must be. Wave w of the 4 * `workgroups`
     multiplies variant w % 16 of the operands, small integers hashed from the
     low 32 bits of `seed`, `iters` times into its 64 x 64 tile, and every
@@ -289,10 +309,28 @@ def mfma_checksum(workgroups: int, iters: int, seed: int, form: str = "bf16") ->
     both at K = 64 under a scale of 2^e per row or column and block of 32 k
     (mxfp8: e in {0, 1} on both sides; mxfp4: 1 + e for A, 1 for B), so that
     every effective element is an integer and the product is taken from
-    integer matrices as for bf16."""
+    integer matrices as for bf16.
+
+    `operands` is one of MFMA_OPERANDS (anything else raises ValueError).
+    With "lds" the four waves of a workgroup share the four variants they
+    built: at step i of the launch wave w multiplies the fragments of slot
+    (w + i) & 3, that is variant v_s = (w & ~3) % 16 + ((w + s) & 3) at the
+    n_s = iters // 4 + (1 if s < iters % 4 else 0) steps with i % 4 = s, so
+    its lane folds to the sum over s = 0..3 of n_s times what one step of
+    v_s adds. With one step that is the wave's own variant, as from
+    registers."""
     sums = _mfma_lane_sums(int(seed) & _M32, _mfma_form_id(form))
     waves = 4 * int(workgroups)
     total = 0
+    if _mfma_operands(operands) == "lds":
+        steps = [int(iters) // 4 + (1 if s < int(iters) % 4 else 0) for s in range(4)]
+        for first in range(min(MFMA_VARIANTS, waves)):  # the waves w % 16 == first
+            mine = range(first, waves, MFMA_VARIANTS)
+            lanes = [sum(n * sums[(first & ~3) + ((first + s) & 3)][lane]
+                         for s, n in enumerate(steps)) for lane in range(64)]
+            total += 64 * sum(mine) * sum(lanes) + len(mine) * sum(
+                (lane + 1) * s for lane, s in enumerate(lanes))
+        return total % (1 << 64)
     for variant, lanes in enumerate(sums):
         mine = range(variant, waves, MFMA_VARIANTS)  # the waves of this variant
         # the sum over them of (64 w + lane + 1) * lanes[lane]
@@ -314,6 +352,7 @@ def _child_parser() -> argparse.ArgumentParser:
     p.add_argument("--passes", type=int, default=0)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--form", choices=MFMA_FORMS, default="bf16")
+    p.add_argument("--operands", choices=MFMA_OPERANDS, default=None)
     return p
 
 
@@ -333,6 +372,10 @@ def child_main(argv: Optional[Sequence[str]] = None, stdin=None, stdout=None) ->
     # would refuse is handed on, so that it does refuse it.
     if args.kind in MATRIX_KINDS or args.form != MFMA_FORMS[0]:
         window["form"] = args.form
+    # Likewise the operands, and only when named: the probe refuses "lds"
+    # beside another kind.
+    if args.operands is not None:
+        window["operands"] = args.operands
     warm = probe.cu_tenant_run(args.device, None, launches=1, **window)
     if "skipped" in warm:
         print(f"cotenancy child: {warm}", file=sys.stderr)
@@ -426,7 +469,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
              iters: int = 0, bytes: int = 0, passes: int = 0, seed: int = 1,
              timeout: float = 120.0,
              spawn: Optional[Callable[[List[str], Dict[str, str]], Any]] = None,
-             form: Optional[str] = None) -> Dict[str, Any]:
+             form: Optional[str] = None,
+             operands: Optional[str] = None) -> Dict[str, Any]:
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
     "fma" | "stream" | "cache" | "chase" | "mfma"} and may carry its own "launches", "iters",
@@ -441,6 +485,13 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     kind, raises ValueError before anything is started. A child is given
     --form only when a form was named for it.
 
+    `operands` (one of MFMA_OPERANDS) says where every mfma tenant of the
+    call takes its operands from, by the same rules: an mfma tenant may
+    carry its own "operands" instead, an unknown value or "operands" on a
+    tenant of another kind raises ValueError before anything is started,
+    and a child is given --operands, after --form, only when one was named
+    for it.
+
     Each child has `timeout` seconds from its start. The first child that
     times out, exits non-zero or prints no TENANT line ends the run: the
     others are killed and {"ok": False, "reason": "child-failed", "detail"}
@@ -451,17 +502,28 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
         raise ValueError("one kind per tenant")
     if form is not None:
         _mfma_form_id(form)
+    if operands is not None:
+        _mfma_operands(operands)
     forms: List[Optional[str]] = []  # per tenant; None: the child is not told
+    sources: List[Optional[str]] = []  # likewise, the tenant's operands
     for i, tenant in enumerate(tenants):
         kind = kinds[i] if kinds is not None else tenant["kind"]
         if kind not in MATRIX_KINDS:
             if tenant.get("form") is not None:
                 raise ValueError(f"a {kind} tenant takes no form: {tenant['form']!r}")
+            if tenant.get("operands") is not None:
+                raise ValueError(
+                    f"a {kind} tenant takes no operands: {tenant['operands']!r}")
             forms.append(None)
+            sources.append(None)
             continue
         forms.append(form if tenant.get("form") is None else tenant["form"])
         if forms[i] is not None:
             _mfma_form_id(forms[i])
+        sources.append(operands if tenant.get("operands") is None
+                       else tenant["operands"])
+        if sources[i] is not None:
+            _mfma_operands(sources[i])
     spawn = _spawn if spawn is None else spawn
     root = str(Path(__file__).resolve().parents[2])
     children: List[_Child] = []
@@ -483,6 +545,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
                     "--seed", str(seed)]
             if forms[i] is not None:
                 argv += ["--form", forms[i]]
+            if sources[i] is not None:
+                argv += ["--operands", sources[i]]
             try:
                 proc = spawn(argv, env)
             except OSError as exc:
@@ -543,7 +607,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                      spawn: Optional[Callable[..., Any]] = None,
                      expected_checksum: Optional[Callable[[int, int], int]] = None,
                      windows: Optional[Mapping[str, Mapping[str, int]]] = None,
-                     form: Optional[str] = None) -> Dict[str, Any]:
+                     form: Optional[str] = None,
+                     operands: Optional[str] = None) -> Dict[str, Any]:
     """Each of two tenants' ({"mask": int}) rate alone and next to the other.
 
     First one solo run per tenant and kind that `pairs` uses, then the pairs
@@ -588,6 +653,16 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     entries, solo and in a pair, add "form". With no form named anywhere the
     children are started as before, run bf16, and no entry has "form".
 
+    `operands` (one of MFMA_OPERANDS, anything else raises ValueError) says
+    where the mfma tenants take their operands from, alone and in every
+    pair: "registers", or "lds" for tenants that re-read them from LDS
+    before every step; a tenant ({"mask": int, "operands": str}) may name
+    its own instead. The other kinds are not touched by it. A tenant's
+    checksum is held against mfma_checksum() of its own form and operands,
+    and its mfma entries, solo and in a pair, add "operands". With none
+    named anywhere the children are started as before, keep their operands
+    in registers, and no entry has "operands".
+
     ok says that the measurement is valid (every child exited 0, every
     stream and cache checksum equals the pattern's, every chase and mfma
     checksum the closed form's, overlap was reached), not that the
@@ -608,6 +683,11 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     for f in forms:
         if f is not None:
             _mfma_form_id(f)
+    sources = [operands if t.get("operands") is None else t["operands"]
+               for t in tenants]
+    for o in sources:
+        if o is not None:
+            _mfma_operands(o)
     expected_checksum = expected_checksum or _pattern_checksum
     window = {"iters": iters, "bytes": bytes, "passes": passes, "seed": seed,
               "timeout": timeout, "spawn": spawn}
@@ -625,6 +705,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         more: Dict[str, Any] = dict(windows.get(kind, {}))
         if kind in MATRIX_KINDS and forms[i] is not None:
             more["form"] = forms[i]
+        if kind in MATRIX_KINDS and sources[i] is not None:
+            more["operands"] = sources[i]
         return more
 
     def sound(result: Mapping[str, Any], i: int) -> Optional[str]:
@@ -644,7 +726,7 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         if result["kind"] in MATRIX_KINDS:
             if int(result["checksum"]) != mfma_checksum(
                     result["workgroups"], result["iters"], seed,
-                    forms[i] or MFMA_FORMS[0]):
+                    forms[i] or MFMA_FORMS[0], sources[i] or MFMA_OPERANDS[0]):
                 return "bad-checksum"
         return None
 
@@ -676,6 +758,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 report["solo"][i][kind]["clock_ghz"] = result["clock_ghz"]
                 if forms[i] is not None:
                     report["solo"][i][kind]["form"] = forms[i]
+                if sources[i] is not None:
+                    report["solo"][i][kind]["operands"] = sources[i]
 
     for pair in pairs:
         name = "/".join(pair)
@@ -708,6 +792,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 "mixed_launches": labels.count("mixed")}
             if pair[i] in MATRIX_KINDS and forms[i] is not None:
                 t["form"] = forms[i]
+            if pair[i] in MATRIX_KINDS and sources[i] is not None:
+                t["operands"] = sources[i]
             if len(rates) < MIN_CONTENDED:
                 why = why or "no-overlap"
             else:

@@ -24,7 +24,8 @@ processes under disjoint masks, each one's rate alone and next to the other.
 --co-tenancy-chase for a tenant bound by the latency of dependent loads,
 --co-tenancy-mfma for a tenant on the matrix cores, whose clock is the
 chip's and follows no mask; --co-tenancy-mfma-form runs that tenant with the
-FP8 or block-scaled MX instructions in place of the bf16 one.
+FP8 or block-scaled MX instructions in place of the bf16 one, and
+--co-tenancy-mfma-operands lds with its operands re-read from LDS every step.
 """
 from __future__ import annotations
 
@@ -139,6 +140,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "rate), mxfp8 and mxfp4 (block-scaled, 2 x and 4 x "
                         "the bf16 work per clock); one report per card and "
                         "form, one after another")
+    p.add_argument("--co-tenancy-mfma-operands", choices=("registers", "lds"),
+                   default=None,
+                   help="with --co-tenancy-mfma: where the MFMA tenants take "
+                        "their operands from: registers (what they do when "
+                        "the flag is absent), or lds, re-read from LDS before "
+                        "every step as a GEMM or attention kernel re-reads "
+                        "its own; combines with --co-tenancy-mfma-form")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -188,23 +196,29 @@ def main(argv=None) -> int:
     if args.co_tenancy_mfma_form is not None and not args.co_tenancy_mfma:
         print("--co-tenancy-mfma-form needs --co-tenancy-mfma", file=sys.stderr)
         return 2
+    if args.co_tenancy_mfma_operands is not None and not args.co_tenancy_mfma:
+        print("--co-tenancy-mfma-operands needs --co-tenancy-mfma", file=sys.stderr)
+        return 2
 
     if args.co_tenancy_mfma:
         from elastic_gpu_scheduler_amd.agent.cotenancy import MFMA_PAIRS
 
         agent = NodeAgent(args.node or "local", client=None,
                           prefer_source=args.source)
+        # Handed on only when the flag is given.
+        more = ({} if args.co_tenancy_mfma_operands is None
+                else {"operands": args.co_tenancy_mfma_operands})
         if args.co_tenancy_mfma_form is not None:
             # One card and one form after another: never more than two
             # children at once.
             print(json.dumps({card: {form: agent.verify_isolation(
-                card, args.co_tenancy, pairs=MFMA_PAIRS, form=form)
+                card, args.co_tenancy, pairs=MFMA_PAIRS, form=form, **more)
                 for form in args.co_tenancy_mfma_form}
                 for card in sorted(agent.mask_layouts())}, indent=2))
             return 0
         # One card after another: never more than two children at once.
         print(json.dumps({card: agent.verify_isolation(
-            card, args.co_tenancy, pairs=MFMA_PAIRS)
+            card, args.co_tenancy, pairs=MFMA_PAIRS, **more)
             for card in sorted(agent.mask_layouts())}, indent=2))
         return 0
 

@@ -6,7 +6,7 @@
 //     working set that every workgroup keeps to itself ("cache"), a walk
 //     along a chain of dependent loads, one in flight per wave ("chase"), or
 //     MFMAs (bf16, or the fp8, mxfp8 or mxfp4 form) issued back to back on
-//     operands held in registers ("mfma"),
+//     operands held in registers or re-read from LDS every step ("mfma"),
 //     each launch stamped with the device's constant-rate wall clock. The
 //     clock is the card's, not the
 //     process's, so two separate processes can lay their launches side by
@@ -303,6 +303,16 @@ constexpr MfmaFormInfo kMfmaFormTable[kMfmaForms] = {
     {"mxfp4", 64, 256, 32768},
 };
 
+// Operands from LDS (tenant_mfma_lds_kernel): a workgroup's image is one slot
+// per wave, and a slot is the bytes a wave reads per step, in planes of 64
+// lanes x 16 bytes: bf16 and mxfp4 one plane per fragment, mxfp8 two, fp8
+// one for A0|A1 and one for B0|B1, the block-scaled forms one more for the
+// scales. LDS per workgroup is 4 slots: 16, 8, 36 and 20 KiB.
+// agent/cotenancy.py keeps the same table.
+constexpr int kMfmaLdsSlots = kWavesPerGroup;
+constexpr int kMfmaLdsPlaneBytes = 64 * 16;
+constexpr int kMfmaLdsStepBytes[kMfmaForms] = {4096, 2048, 9216, 5120};
+
 // The hashes behind A[row][k] and B[k][col] of one operand variant and, for
 // the block-scaled forms, behind the scale of a row's or column's block of 32
 // k. Hashed, so nothing is symmetric in its two indices; for bf16 (F = 0) the
@@ -383,6 +393,21 @@ struct MfmaFrags<kBf16> {
   __device__ f32x16 mfma(int m, int n, f32x16 c) const {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m], b[n], c, 0, 0, 0);
   }
+  static constexpr int kLdsPlanes = 4;  // A0, A1, B0, B1
+  __device__ void to_lds(int4v* slot, uint32_t lane) const {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      slot[64 * t + lane] = __builtin_bit_cast(int4v, a[t]);
+      slot[64 * (2 + t) + lane] = __builtin_bit_cast(int4v, b[t]);
+    }
+  }
+  __device__ void from_lds(const int4v* slot, uint32_t lane) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      a[t] = __builtin_bit_cast(bf16x8, slot[64 * t + lane]);
+      b[t] = __builtin_bit_cast(bf16x8, slot[64 * (2 + t) + lane]);
+    }
+  }
 };
 
 template <>
@@ -410,6 +435,22 @@ struct MfmaFrags<kFp8> {
   }
   __device__ f32x16 mfma(int m, int n, f32x16 c) const {
     return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a[m], b[n], c, 0, 0, 0);
+  }
+  // A fragment is 8 bytes per lane: A0|A1 side by side in one plane, B0|B1
+  // in the other, so that the reads are 16 bytes wide like every other form's.
+  static constexpr int kLdsPlanes = 2;
+  using long2v = __attribute__((ext_vector_type(2))) long;
+  __device__ void to_lds(int4v* slot, uint32_t lane) const {
+    slot[lane] = __builtin_bit_cast(int4v, long2v{a[0], a[1]});
+    slot[64 + lane] = __builtin_bit_cast(int4v, long2v{b[0], b[1]});
+  }
+  __device__ void from_lds(const int4v* slot, uint32_t lane) {
+    const long2v av = __builtin_bit_cast(long2v, slot[lane]);
+    const long2v bv = __builtin_bit_cast(long2v, slot[64 + lane]);
+    a[0] = av[0];
+    a[1] = av[1];
+    b[0] = bv[0];
+    b[1] = bv[1];
   }
 };
 
@@ -448,6 +489,33 @@ struct MfmaFrags<kMxfp8> {
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[m], b[n], c, 0, 0, 0, sa[m], 0,
                                                            sb[n]);
   }
+  // Two planes per fragment, the lane's low four dwords and its high four,
+  // in the order A0, A1, B0, B1, then the plane of {sa[0], sa[1], sb[0], sb[1]}.
+  static constexpr int kLdsPlanes = 9;
+  __device__ void to_lds(int4v* slot, uint32_t lane) const {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      slot[64 * (2 * t) + lane] = int4v{a[t][0], a[t][1], a[t][2], a[t][3]};
+      slot[64 * (2 * t + 1) + lane] = int4v{a[t][4], a[t][5], a[t][6], a[t][7]};
+      slot[64 * (4 + 2 * t) + lane] = int4v{b[t][0], b[t][1], b[t][2], b[t][3]};
+      slot[64 * (5 + 2 * t) + lane] = int4v{b[t][4], b[t][5], b[t][6], b[t][7]};
+    }
+    slot[64 * 8 + lane] = int4v{sa[0], sa[1], sb[0], sb[1]};
+  }
+  __device__ void from_lds(const int4v* slot, uint32_t lane) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int4v al = slot[64 * (2 * t) + lane], ah = slot[64 * (2 * t + 1) + lane];
+      const int4v bl = slot[64 * (4 + 2 * t) + lane], bh = slot[64 * (5 + 2 * t) + lane];
+      a[t] = int8v{al[0], al[1], al[2], al[3], ah[0], ah[1], ah[2], ah[3]};
+      b[t] = int8v{bl[0], bl[1], bl[2], bl[3], bh[0], bh[1], bh[2], bh[3]};
+    }
+    const int4v s = slot[64 * 8 + lane];
+    sa[0] = s[0];
+    sa[1] = s[1];
+    sb[0] = s[2];
+    sb[1] = s[3];
+  }
 };
 
 template <>
@@ -484,6 +552,27 @@ struct MfmaFrags<kMxfp4> {
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[m]), widen(b[n]), c, 4, 4,
                                                            0, sa[m], 0, sb[n]);
   }
+  static constexpr int kLdsPlanes = 5;  // A0, A1, B0, B1, {sa[0], sa[1], sb[0], sb[1]}
+  __device__ void to_lds(int4v* slot, uint32_t lane) const {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      slot[64 * t + lane] = a[t];
+      slot[64 * (2 + t) + lane] = b[t];
+    }
+    slot[64 * 4 + lane] = int4v{sa[0], sa[1], sb[0], sb[1]};
+  }
+  __device__ void from_lds(const int4v* slot, uint32_t lane) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      a[t] = slot[64 * t + lane];
+      b[t] = slot[64 * (2 + t) + lane];
+    }
+    const int4v s = slot[64 * 4 + lane];
+    sa[0] = s[0];
+    sa[1] = s[1];
+    sb[0] = s[2];
+    sb[1] = s[3];
+  }
 };
 
 // Every wave owns a 64x64 output tile, 2 x 2 accumulators of 32x32, and keeps
@@ -505,6 +594,54 @@ struct MfmaFrags<kMxfp4> {
 // every workgroup reads s_memtime next to each end of its wall-clock interval
 // and adds both differences. cycles / ticks x tick_hz is the shader clock the
 // launch ran at, averaged over its workgroups.
+using MfmaTile = f32x16[2][2];
+
+// The key of the variant that global wave w builds.
+__device__ inline uint32_t mfma_key(uint32_t seed32, uint32_t w) {
+  return mix32(seed32 ^ ((w % kMfmaVariants) * 0x9E3779B1u));
+}
+
+__device__ inline void mfma_zero(MfmaTile& acc) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) acc[t >> 1][t & 1][reg] = 0.0f;
+}
+
+// One step: acc[m][n] += A_m x B_n.
+template <int F>
+__device__ inline void mfma_step(const MfmaFrags<F>& frags, MfmaTile& acc) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    acc[t >> 1][t & 1] = frags.mfma(t >> 1, t & 1, acc[t >> 1][t & 1]);
+}
+
+// Adds a chunk to the lane's fold.
+__device__ inline void mfma_fold(const MfmaTile& acc, uint64_t& fold) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg)
+      fold += static_cast<uint64_t>(static_cast<int64_t>(
+                  static_cast<int>(acc[t >> 1][t & 1][reg]))) *
+              static_cast<uint64_t>(1 + reg + 16 * t);
+}
+
+// The lane's store, the end stamp and the workgroup's share of clk.
+__device__ inline void mfma_finish(unsigned long long* __restrict__ out,
+                                   unsigned long long* __restrict__ rec,
+                                   unsigned long long* __restrict__ clk, uint64_t fold,
+                                   unsigned long long c0, unsigned long long t0) {
+  out[static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x] = fold;
+  stamp_end(rec, t0);
+  if (threadIdx.x == 0) {
+    const unsigned long long c1 = __builtin_amdgcn_s_memtime();
+    const unsigned long long t1 = wall_clock64();
+    atomicAdd(&clk[0], c1 - c0);
+    atomicAdd(&clk[1], t1 - t0);
+  }
+}
+
 template <int F>
 __global__ void __launch_bounds__(kBlock)
 tenant_mfma_kernel(uint32_t seed32, int iters, unsigned long long* __restrict__ out,
@@ -514,9 +651,8 @@ tenant_mfma_kernel(uint32_t seed32, int iters, unsigned long long* __restrict__ 
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t r = lane & 31u, h = lane >> 5;
   const uint32_t w = blockIdx.x * kWavesPerGroup + threadIdx.x / 64;
-  const uint32_t key = mix32(seed32 ^ ((w % kMfmaVariants) * 0x9E3779B1u));
   MfmaFrags<F> frags;
-  frags.build(key, r, h);
+  frags.build(mfma_key(seed32, w), r, h);
   // The fragments are in their registers before either clock is read.
   frags.pin();
   const unsigned long long c0 = __builtin_amdgcn_s_memtime();
@@ -525,31 +661,107 @@ tenant_mfma_kernel(uint32_t seed32, int iters, unsigned long long* __restrict__ 
   for (int done = 0; done < iters; done += kChunk) {
     const int steps = min(iters - done, kChunk);
     f32x16 acc[2][2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) acc[t >> 1][t & 1][reg] = 0.0f;
-    for (int i = 0; i < steps; ++i) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        acc[t >> 1][t & 1] = frags.mfma(t >> 1, t & 1, acc[t >> 1][t & 1]);
+    mfma_zero(acc);
+    for (int i = 0; i < steps; ++i) mfma_step(frags, acc);
+    mfma_fold(acc, fold);
+  }
+  mfma_finish(out, rec, clk, fold, c0, t0);
+}
+
+// The order of a step of tenant_mfma_lds_kernel: the step's `reads` LDS reads
+// spread over the gaps in front of its first three MFMAs, at most `per_gap`
+// in each, so that no gap carries more reads than the LDS array serves
+// beside the MFMA, and none is issued later than three MFMAs before the
+// step that needs it.
+template <int reads, int per_gap>
+__device__ inline void mfma_lds_interleave() {
+  constexpr int n0 = reads < per_gap ? reads : per_gap;
+  constexpr int n1 = reads - n0 < per_gap ? reads - n0 : per_gap;
+  constexpr int n2 = reads - n0 - n1;
+  static_assert(n2 <= per_gap + 1, "the reads fit the first three gaps");
+  __builtin_amdgcn_sched_group_barrier(0x100, n0, 0);  // DS reads
+  __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+  __builtin_amdgcn_sched_group_barrier(0x100, n1, 0);
+  __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+  __builtin_amdgcn_sched_group_barrier(0x100, n2, 0);
+  __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+}
+
+// The same tenant with its operands re-read from LDS before every step, as a
+// GEMM or an attention kernel re-reads its own. Grid, tile, the four MFMAs of
+// a step, chunks, fold, stamps and cycle sums are tenant_mfma_kernel's.
+//
+// Before either clock is read, wave j (0..3) of workgroup b builds the
+// fragments of its own variant (4b + j) % 16, as above, and stores them to
+// slot j of the workgroup's image (layout: MfmaFrags<F>::to_lds and the table
+// at kMfmaLdsStepBytes: every fragment lane-contiguous in planes of 16 bytes
+// per lane, address = plane base + 16 x lane, so every read is a 16-byte one
+// in which no two lanes of a group share a bank); a workgroup barrier closes
+// the fill. At step i of the launch, counted across chunks, global wave w
+// multiplies the fragments of slot (w + i) & 3, which are those of variant
+// (w & ~3) % 16 + ((w + i) & 3). The slot index is masked to 0..3, so every
+// address is inside the image.
+//
+// Two register sets: the reads of step i + 1 are issued in front of the first
+// three MFMAs of step i (mfma_lds_interleave) and are first needed after its
+// last, so that one wave per SIMD hides the LDS latency behind its own MFMAs
+// (the wait is the counted one the compiler places in front of the first
+// use). The last step of a launch reads one slot
+// more than it multiplies. The slot changes every step and a compiler barrier
+// closes every step, so nothing a wave read for one step stands in for a
+// later one. Nothing is read from global memory between the stamps.
+//
+// The per-step bounds on |A x B| hold for every variant, so the chunks and the
+// exactness argument above (every partial sum below 2^23) carry over
+// unchanged; the fold is linear in the number of steps of each of the four
+// slots (agent/cotenancy.py, mfma_checksum(operands="lds")).
+template <int F>
+__global__ void __launch_bounds__(kBlock)
+tenant_mfma_lds_kernel(uint32_t seed32, int iters, unsigned long long* __restrict__ out,
+                       unsigned long long* __restrict__ rec,
+                       unsigned long long* __restrict__ clk) {
+  constexpr int kChunk = kMfmaFormTable[F].chunk;
+  constexpr int kSlotVecs = MfmaFrags<F>::kLdsPlanes * 64;
+  static_assert(kSlotVecs * 16 == kMfmaLdsStepBytes[F], "the table is the layout's");
+  // Two 16-byte reads per 32 cycles of MFMA.
+  constexpr int kReadsPerGap = F == kMxfp8 ? 4 : 2;
+  static_assert(kChunk % 4 == 0, "a chunk starts on the first register set and on slot j");
+  __shared__ int4v image[kMfmaLdsSlots][kSlotVecs];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = lane & 31u, h = lane >> 5;
+  const uint32_t j = threadIdx.x / 64;
+  const uint32_t w = blockIdx.x * kWavesPerGroup + j;
+  MfmaFrags<F> f0, f1;
+  f0.build(mfma_key(seed32, w), r, h);
+  f0.to_lds(image[j], lane);
+  __syncthreads();
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  const unsigned long long t0 = stamp_start();
+  uint64_t fold = 0;
+  f0.from_lds(image[j], lane);  // step 0
+  for (int done = 0; done < iters; done += kChunk) {
+    const int steps = min(iters - done, kChunk);
+    f32x16 acc[2][2];
+    mfma_zero(acc);
+    // Step done + i multiplies slot (j + done + i) & 3; done is a multiple of 4.
+    int i = 0;
+    for (; i + 1 < steps; i += 2) {
+      f1.from_lds(image[(j + i + 1) & 3u], lane);
+      mfma_step(f0, acc);
+      mfma_lds_interleave<MfmaFrags<F>::kLdsPlanes, kReadsPerGap>();
+      asm volatile("" ::: "memory");
+      f0.from_lds(image[(j + i + 2) & 3u], lane);
+      mfma_step(f1, acc);
+      mfma_lds_interleave<MfmaFrags<F>::kLdsPlanes, kReadsPerGap>();
+      asm volatile("" ::: "memory");
     }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg)
-        fold += static_cast<uint64_t>(static_cast<int64_t>(
-                    static_cast<int>(acc[t >> 1][t & 1][reg]))) *
-                static_cast<uint64_t>(1 + reg + 16 * t);
+    if (i < steps) {  // an odd last chunk
+      mfma_step(f0, acc);
+      asm volatile("" ::: "memory");
+    }
+    mfma_fold(acc, fold);
   }
-  out[static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x] = fold;
-  stamp_end(rec, t0);
-  if (threadIdx.x == 0) {
-    const unsigned long long c1 = __builtin_amdgcn_s_memtime();
-    const unsigned long long t1 = wall_clock64();
-    atomicAdd(&clk[0], c1 - c0);
-    atomicAdd(&clk[1], t1 - t0);
-  }
+  mfma_finish(out, rec, clk, fold, c0, t0);
 }
 
 // ---- host ------------------------------------------------------------------
@@ -568,6 +780,8 @@ struct TenantResult {
   uint64_t free_bytes = 0;
   Kind kind = Kind::kFma;
   int form = kBf16;  // mfma only
+  bool lds = false;  // mfma only: operands re-read from LDS
+  uint64_t lds_bytes = 0, lds_bytes_per_launch = 0;  // mfma from LDS only
   MaskWords applied;
   double tick_hz = 0.0;
   int workgroups = 0;
@@ -584,7 +798,8 @@ struct TenantResult {
 };
 
 TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int launches,
-                        int iters, uint64_t bytes, int passes, uint64_t seed, int form) {
+                        int iters, uint64_t bytes, int passes, uint64_t seed, int form,
+                        bool lds) {
   require_device(device);
   const int cus = gpuprobe::device_cus(device);
   const MaskWords mask =
@@ -619,6 +834,12 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     r.work_per_launch = static_cast<double>(grid) * kWavesPerGroup *
                         static_cast<double>(r.iters) * 4.0 * kMfmaFlopsPerK *
                         kMfmaFormTable[form].k;
+    r.lds = lds;
+    if (lds) {
+      r.lds_bytes = static_cast<uint64_t>(kMfmaLdsSlots) * kMfmaLdsStepBytes[form];
+      r.lds_bytes_per_launch = static_cast<uint64_t>(grid) * kWavesPerGroup *
+                               static_cast<uint64_t>(r.iters) * kMfmaLdsStepBytes[form];
+    }
   } else {
     const bool cache = kind == Kind::kCache;
     if (chase) {
@@ -684,10 +905,15 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
   {
     StreamGuard g;
     gpuprobe::open_stream(g, mask, r.applied);
-    const auto mfma_kernel = form == kFp8     ? tenant_mfma_kernel<kFp8>
-                             : form == kMxfp8 ? tenant_mfma_kernel<kMxfp8>
-                             : form == kMxfp4 ? tenant_mfma_kernel<kMxfp4>
-                                              : tenant_mfma_kernel<kBf16>;
+    const auto mfma_kernel =
+        lds ? (form == kFp8     ? tenant_mfma_lds_kernel<kFp8>
+               : form == kMxfp8 ? tenant_mfma_lds_kernel<kMxfp8>
+               : form == kMxfp4 ? tenant_mfma_lds_kernel<kMxfp4>
+                                : tenant_mfma_lds_kernel<kBf16>)
+            : (form == kFp8     ? tenant_mfma_kernel<kFp8>
+               : form == kMxfp8 ? tenant_mfma_kernel<kMxfp8>
+               : form == kMxfp4 ? tenant_mfma_kernel<kMxfp4>
+                                : tenant_mfma_kernel<kBf16>);
     auto launch = [&](int slot) {
       unsigned long long* rec = recs.as<unsigned long long>() + 2 * slot;
       if (kind == Kind::kFma)
@@ -800,7 +1026,8 @@ void register_cotenant(py::module_& m) {
   m.def(
       "cu_tenant_run",
       [](int device, py::object mask, const std::string& kind, int launches, int iters,
-         uint64_t bytes, int passes, uint64_t seed, const std::string& form) {
+         uint64_t bytes, int passes, uint64_t seed, const std::string& form,
+         const std::string& operands) {
         const MaskWords words = gpuprobe::mask_from_python(mask);
         Kind k;
         if (kind == "fma")
@@ -827,10 +1054,18 @@ void register_cotenant(py::module_& m) {
               "cu_tenant_run: form \"" + form + "\" needs kind \"mfma\"; of the forms "
               "\"bf16\", \"fp8\", \"mxfp8\" and \"mxfp4\" every other kind takes only "
               "\"bf16\"");
+        if (operands != "registers" && operands != "lds")
+          throw py::value_error(
+              "cu_tenant_run: operands must be \"registers\" or \"lds\"");
+        const bool lds = operands == "lds";
+        if (lds && k != Kind::kMfma)
+          throw py::value_error(
+              "cu_tenant_run: operands \"lds\" needs kind \"mfma\"; of the operands "
+              "\"registers\" and \"lds\" every other kind takes only \"registers\"");
         TenantResult r;
         {
           py::gil_scoped_release release;
-          r = run_tenant(device, words, k, launches, iters, bytes, passes, seed, f);
+          r = run_tenant(device, words, k, launches, iters, bytes, passes, seed, f, lds);
         }
         py::dict d;
         if (r.skipped) {
@@ -849,6 +1084,11 @@ void register_cotenant(py::module_& m) {
           d["form"] = kMfmaFormTable[r.form].name;
           d["iters"] = r.iters;
           d["checksum"] = r.checksum;
+          if (r.lds) {
+            d["operands"] = operands;
+            d["lds_bytes"] = r.lds_bytes;
+            d["lds_bytes_per_launch"] = r.lds_bytes_per_launch;
+          }
         } else if (k == Kind::kChase) {
           d["bytes"] = r.bytes;
           d["nodes"] = r.nodes;
@@ -886,6 +1126,7 @@ void register_cotenant(py::module_& m) {
       py::arg("device") = 0, py::arg("mask") = py::none(), py::arg("kind") = "fma",
       py::arg("launches") = 8, py::arg("iters") = 0, py::arg("bytes") = 0,
       py::arg("passes") = 0, py::arg("seed") = 1, py::arg("form") = "bf16",
+      py::arg("operands") = "registers",
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
@@ -1007,10 +1248,38 @@ void register_cotenant(py::module_& m) {
       "alike. A chunk's partial "
       "sums stay below 2048 * 3600, 512 * 12544 and 256 * 18432, all below "
       "2^23, so mfma_checksum(..., form) is exact for every form.\n\n"
+      "mfma, `operands`: \"registers\" (the default, everything above) or "
+      "\"lds\"; anything else, or \"lds\" with a kind other than \"mfma\", "
+      "raises ValueError before the device is touched. With \"lds\" every "
+      "step's fragments are re-read from LDS, for every form; grid, tile, "
+      "steps, chunks, fold, clocks, `iters` and its defaults are the same. "
+      "Before anything is timed wave j (0..3) of workgroup b builds the "
+      "fragments of its own variant (4 b + j) % 16 and stores them to slot j "
+      "of the workgroup's static LDS image of 4 slots; a slot holds A0, A1, "
+      "B0, B1 lane-contiguous in planes of 16 bytes per lane (address = plane "
+      "base + 16 * lane, so every read is a conflict-free ds_read_b128): one "
+      "plane per fragment for bf16 and mxfp4, two for mxfp8 (the lane's low "
+      "four dwords, then its high four), for fp8 one plane A0|A1 and one "
+      "B0|B1 (8 bytes each, side by side), and for the block-scaled forms one "
+      "more plane of {sa[0], sa[1], sb[0], sb[1]}: 4096, 2048, 9216 and 5120 "
+      "bytes per slot, 16, 8, 36 and 20 KiB per workgroup (bf16, fp8, mxfp8, "
+      "mxfp4). At step i of the launch, counted across chunks, global wave w "
+      "multiplies the fragments of slot (w + i) & 3, that is variant (w & ~3) "
+      "% 16 + ((w + i) & 3); the reads of step i + 1 are issued in front of the "
+      "first three MFMAs of step i, at most two per 32 cycles of MFMA, into a "
+      "second register set, and nothing is read from "
+      "global memory between the stamps. At full MFMA rate that is 128, 64, "
+      "144 and 160 B per clock and CU, below the LDS array's 256. The bounds "
+      "per step hold for every variant, so the chunks stay exact; the result "
+      "adds operands, lds_bytes (per workgroup) and lds_bytes_per_launch = "
+      "waves * iters * the form's bytes per slot, and its checksum equals "
+      "mfma_checksum(..., form, \"lds\"). With \"registers\" the result has "
+      "none of the three.\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
       "{kind, [form,] applied_mask, tick_hz, workgroups, iters | bytes, passes, checksum, "
+      "[operands, lds_bytes, lds_bytes_per_launch,] "
       "[bytes_per_cu,] work_per_launch: flops, bytes or hops, launches: [{t0, t1, "
       "seconds: (t1 - t0) "
       "/ tick_hz, event_seconds, rate[, cycles, ticks, clock_ghz]}], rate[, "
