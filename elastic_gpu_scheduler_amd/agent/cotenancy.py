@@ -280,17 +280,29 @@ def _mfma_lane_sums(seed32: int, form: int = 0) -> Tuple[Tuple[int, ...], ...]:
     return tuple(out)
 
 
-def _mfma_form_id(form: Optional[str]) -> int:
-    if form not in MFMA_FORMS:
-        raise ValueError(f"unknown mfma form {form!r}: one of " + ", ".join(MFMA_FORMS))
-    return MFMA_FORMS.index(form)
+# What an mfma tenant may be told beyond its window, in the order its child
+# is told, each with the values it may take.
+_MFMA_OPTIONS = {"form": MFMA_FORMS, "operands": MFMA_OPERANDS}
 
 
-def _mfma_operands(operands: Optional[str]) -> str:
-    if operands not in MFMA_OPERANDS:
-        raise ValueError(f"unknown mfma operands {operands!r}: one of "
-                         + ", ".join(MFMA_OPERANDS))
-    return operands
+def _checked(key: str, value: Optional[str]) -> str:
+    if value not in _MFMA_OPTIONS[key]:
+        raise ValueError(f"unknown mfma {key} {value!r}: one of "
+                         + ", ".join(_MFMA_OPTIONS[key]))
+    return value
+
+
+def _mfma_option(key: str, tenant: Mapping[str, Any], kind: str,
+                 wide: Optional[str]) -> Optional[str]:
+    """The option `key` that `tenant`, run as `kind`, is started with: its
+    own, else the call-wide `wide`; None when neither names one."""
+    own = tenant.get(key)
+    if kind not in MATRIX_KINDS:
+        if own is not None:
+            raise ValueError(f"a {kind} tenant takes no {key}: {own!r}")
+        return None
+    value = wide if own is None else own
+    return value if value is None else _checked(key, value)
 
 
 def mfma_checksum(workgroups: int, iters: int, seed: int, form: str = "bf16",
@@ -319,10 +331,10 @@ def mfma_checksum(workgroups: int, iters: int, seed: int, form: str = "bf16",
     its lane folds to the sum over s = 0..3 of n_s times what one step of
     v_s adds. With one step that is the wave's own variant, as from
     registers."""
-    sums = _mfma_lane_sums(int(seed) & _M32, _mfma_form_id(form))
+    sums = _mfma_lane_sums(int(seed) & _M32, MFMA_FORMS.index(_checked("form", form)))
     waves = 4 * int(workgroups)
     total = 0
-    if _mfma_operands(operands) == "lds":
+    if _checked("operands", operands) == "lds":
         steps = [int(iters) // 4 + (1 if s < int(iters) % 4 else 0) for s in range(4)]
         for first in range(min(MFMA_VARIANTS, waves)):  # the waves w % 16 == first
             mine = range(first, waves, MFMA_VARIANTS)
@@ -500,30 +512,16 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
         raise ValueError("run_pair takes one or two tenants")
     if kinds is not None and len(kinds) != len(tenants):
         raise ValueError("one kind per tenant")
-    if form is not None:
-        _mfma_form_id(form)
-    if operands is not None:
-        _mfma_operands(operands)
-    forms: List[Optional[str]] = []  # per tenant; None: the child is not told
-    sources: List[Optional[str]] = []  # likewise, the tenant's operands
+    call = {"form": form, "operands": operands}
+    for key, value in call.items():
+        if value is not None:
+            _checked(key, value)
+    # Per tenant, what its child is told of each option; None: nothing.
+    options: List[Dict[str, Optional[str]]] = []
     for i, tenant in enumerate(tenants):
         kind = kinds[i] if kinds is not None else tenant["kind"]
-        if kind not in MATRIX_KINDS:
-            if tenant.get("form") is not None:
-                raise ValueError(f"a {kind} tenant takes no form: {tenant['form']!r}")
-            if tenant.get("operands") is not None:
-                raise ValueError(
-                    f"a {kind} tenant takes no operands: {tenant['operands']!r}")
-            forms.append(None)
-            sources.append(None)
-            continue
-        forms.append(form if tenant.get("form") is None else tenant["form"])
-        if forms[i] is not None:
-            _mfma_form_id(forms[i])
-        sources.append(operands if tenant.get("operands") is None
-                       else tenant["operands"])
-        if sources[i] is not None:
-            _mfma_operands(sources[i])
+        options.append({key: _mfma_option(key, tenant, kind, wide)
+                        for key, wide in call.items()})
     spawn = _spawn if spawn is None else spawn
     root = str(Path(__file__).resolve().parents[2])
     children: List[_Child] = []
@@ -543,10 +541,9 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
                     "--bytes", str(tenant.get("bytes", bytes)),
                     "--passes", str(tenant.get("passes", passes)),
                     "--seed", str(seed)]
-            if forms[i] is not None:
-                argv += ["--form", forms[i]]
-            if sources[i] is not None:
-                argv += ["--operands", sources[i]]
+            for key, value in options[i].items():
+                if value is not None:
+                    argv += ["--" + key, value]
             try:
                 proc = spawn(argv, env)
             except OSError as exc:
@@ -598,6 +595,26 @@ def _balanced(launches: int, seconds: Sequence[float]) -> List[int]:
         else:
             out.append(min(MAX_LAUNCHES, math.ceil(2.0 * launches * longest / s) + 1))
     return out
+
+
+# What a report knows of each kind. First the keys of a child's result that a
+# solo entry adds; a kind that adds clock_ghz gets the clock split in a pair.
+_SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",)}
+
+
+def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
+              operands=None) -> Optional[int]:
+    """The checksum a child's result must carry by the oracle of its kind
+    (`pattern` is the reading kinds'); None for a kind that has none."""
+    kind = result["kind"]
+    if kind in READING_KINDS:
+        return pattern(seed, int(result["bytes"]))
+    if kind == "chase":
+        return chase_checksum(result["bytes"], result["workgroups"], result["iters"], seed)
+    if kind in MATRIX_KINDS:
+        return mfma_checksum(result["workgroups"], result["iters"], seed,
+                             form or MFMA_FORMS[0], operands or MFMA_OPERANDS[0])
+    return None
 
 
 def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
@@ -679,20 +696,14 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     for kind, w in windows.items():
         if kind not in ALL_KINDS or any(k not in WINDOW_KEYS for k in w):
             raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
-    forms = [form if t.get("form") is None else t["form"] for t in tenants]
-    for f in forms:
-        if f is not None:
-            _mfma_form_id(f)
-    sources = [operands if t.get("operands") is None else t["operands"]
-               for t in tenants]
-    for o in sources:
-        if o is not None:
-            _mfma_operands(o)
-    expected_checksum = expected_checksum or _pattern_checksum
+    # Per option and tenant, what the tenant is started with as an mfma one.
+    named = {key: [_mfma_option(key, t, MATRIX_KINDS[0], wide) for t in tenants]
+             for key, wide in (("form", form), ("operands", operands))}
+    # The pattern's oracle, asked once per size.
+    pattern = functools.lru_cache(maxsize=None)(expected_checksum or _pattern_checksum)
     window = {"iters": iters, "bytes": bytes, "passes": passes, "seed": seed,
               "timeout": timeout, "spawn": spawn}
     report: Dict[str, Any] = {"ok": True, "solo": [{}, {}], "pairs": {}}
-    checksums: Dict[int, int] = {}
 
     def flaw(reason: str, **more: Any) -> None:
         report["ok"] = False
@@ -700,34 +711,22 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         for k, v in more.items():
             report.setdefault(k, v)
 
+    def options(i: int, kind: str) -> Dict[str, str]:
+        """The options named for tenant i, if `kind` takes any."""
+        found = {key: _mfma_option(key, {}, kind, own[i]) for key, own in named.items()}
+        return {key: value for key, value in found.items() if value is not None}
+
     def asked(i: int, kind: str) -> Dict[str, Any]:
         """What tenant i is started with as `kind`, beyond mask and launches."""
-        more: Dict[str, Any] = dict(windows.get(kind, {}))
-        if kind in MATRIX_KINDS and forms[i] is not None:
-            more["form"] = forms[i]
-        if kind in MATRIX_KINDS and sources[i] is not None:
-            more["operands"] = sources[i]
-        return more
+        return {**windows.get(kind, {}), **options(i, kind)}
 
     def sound(result: Mapping[str, Any], i: int) -> Optional[str]:
         """Why the result of tenant i's child cannot be used, or None."""
         if "skipped" in result:
             return "insufficient-memory"
-        if result["kind"] in READING_KINDS:
-            size = int(result["bytes"])
-            if size not in checksums:
-                checksums[size] = expected_checksum(seed, size)
-            if int(result["checksum"]) != checksums[size]:
-                return "bad-checksum"
-        if result["kind"] == "chase":
-            if int(result["checksum"]) != chase_checksum(
-                    result["bytes"], result["workgroups"], result["iters"], seed):
-                return "bad-checksum"
-        if result["kind"] in MATRIX_KINDS:
-            if int(result["checksum"]) != mfma_checksum(
-                    result["workgroups"], result["iters"], seed,
-                    forms[i] or MFMA_FORMS[0], sources[i] or MFMA_OPERANDS[0]):
-                return "bad-checksum"
+        expected = _expected(result, seed, pattern, **options(i, result["kind"]))
+        if expected is not None and int(result["checksum"]) != expected:
+            return "bad-checksum"
         return None
 
     for i, tenant in enumerate(tenants):
@@ -751,15 +750,9 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 "rate": result["rate"],
                 "seconds": statistics.median(l["seconds"] for l in result["launches"]),
                 "launches": len(result["launches"]),
-                "workgroups": result.get("workgroups")}
-            if kind == "chase":
-                report["solo"][i][kind]["ns_per_hop"] = result["ns_per_hop"]
-            if kind in MATRIX_KINDS:
-                report["solo"][i][kind]["clock_ghz"] = result["clock_ghz"]
-                if forms[i] is not None:
-                    report["solo"][i][kind]["form"] = forms[i]
-                if sources[i] is not None:
-                    report["solo"][i][kind]["operands"] = sources[i]
+                "workgroups": result.get("workgroups"),
+                **{key: result[key] for key in _SOLO_KEYS.get(kind, ())},
+                **options(i, kind)}
 
     for pair in pairs:
         name = "/".join(pair)
@@ -789,17 +782,14 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                 "kind": pair[i], "solo_rate": solo_rate,
                 "contended_launches": len(rates), "launches": len(mine),
                 "solo_launches": labels.count("solo"),
-                "mixed_launches": labels.count("mixed")}
-            if pair[i] in MATRIX_KINDS and forms[i] is not None:
-                t["form"] = forms[i]
-            if pair[i] in MATRIX_KINDS and sources[i] is not None:
-                t["operands"] = sources[i]
+                "mixed_launches": labels.count("mixed"),
+                **options(i, pair[i])}
             if len(rates) < MIN_CONTENDED:
                 why = why or "no-overlap"
             else:
                 t["contended_rate"] = statistics.median(rates)
                 t["ratio"] = t["contended_rate"] / solo_rate
-                if pair[i] in MATRIX_KINDS:
+                if "clock_ghz" in _SOLO_KEYS.get(pair[i], ()):
                     clocks = [l["clock_ghz"] for l, lab in zip(mine, labels)
                               if lab == "contended"]
                     t["solo_clock_ghz"] = report["solo"][i][pair[i]]["clock_ghz"]
@@ -814,6 +804,31 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
             entry["tenants"].append(t)
         report["pairs"][name] = entry
     return report
+
+
+def _profile(card: int, mask: int, kind: str, sizes: Sequence[int], window: Callable,
+             row: Callable, pattern: Optional[Callable], seed: int, **how: Any):
+    """The loop of cache_profile and chase_profile: one child per size, given
+    `bytes` = the size and window(size); a row is row(its result, the median
+    of its launches' seconds)."""
+    out: Dict[str, Any] = {"ok": True, "profile": []}
+    for size in sizes:
+        size = int(size)
+        run = run_pair(card, [{"mask": mask, "kind": kind, "bytes": size,
+                               **window(size)}], seed=seed, **how)
+        if not run["ok"]:
+            out.update(ok=False, reason=run["reason"], detail=run["detail"])
+            return out
+        result = run["tenants"][0]
+        if "skipped" in result:
+            out.update(ok=False, reason="insufficient-memory")
+            return out
+        if int(result["checksum"]) != _expected(result, seed, pattern):
+            out["ok"] = False
+            out.setdefault("reason", "bad-checksum")
+        out["profile"].append(row(result, statistics.median(
+            l["seconds"] for l in result["launches"])))
+    return out
 
 
 def cache_profile(card: int, mask: int, sizes: Sequence[int], *,
@@ -832,30 +847,14 @@ def cache_profile(card: int, mask: int, sizes: Sequence[int], *,
     The first child that fails ends the sweep ("child-failed"), as does one
     that finds too little free memory; a wrong checksum makes it not ok but
     the figures are kept. Nothing is retried."""
-    expected_checksum = expected_checksum or _pattern_checksum
-    out: Dict[str, Any] = {"ok": True, "profile": []}
-    for size in sizes:
-        size = int(size)
-        run = run_pair(card, [{
-            "mask": mask, "kind": "cache", "bytes": size,
-            "passes": passes or cache_passes(size, PROFILE_LAUNCH_BYTES)}],
-            launches=launches, seed=seed, timeout=timeout, spawn=spawn)
-        if not run["ok"]:
-            out.update(ok=False, reason=run["reason"], detail=run["detail"])
-            return out
-        result = run["tenants"][0]
-        if "skipped" in result:
-            out.update(ok=False, reason="insufficient-memory")
-            return out
-        if int(result["checksum"]) != expected_checksum(seed, int(result["bytes"])):
-            out["ok"] = False
-            out.setdefault("reason", "bad-checksum")
-        out["profile"].append({
+    return _profile(
+        card, mask, "cache", sizes,
+        lambda size: {"passes": passes or cache_passes(size, PROFILE_LAUNCH_BYTES)},
+        lambda result, seconds: {
             "bytes": result["bytes"], "bytes_per_cu": result.get("bytes_per_cu"),
-            "rate": result["rate"],
-            "seconds": statistics.median(l["seconds"] for l in result["launches"]),
-            "passes": result["passes"]})
-    return out
+            "rate": result["rate"], "seconds": seconds, "passes": result["passes"]},
+        expected_checksum or _pattern_checksum, seed,
+        launches=launches, timeout=timeout, spawn=spawn)
 
 
 def chase_profile(card: int, mask: int, sizes: Sequence[int], *,
@@ -874,28 +873,13 @@ def chase_profile(card: int, mask: int, sizes: Sequence[int], *,
     The first child that fails ends the sweep ("child-failed"), as does one
     that finds too little free memory; a wrong checksum (chase_checksum)
     makes it not ok but the figures are kept. Nothing is retried."""
-    out: Dict[str, Any] = {"ok": True, "profile": []}
-    for size in sizes:
-        run = run_pair(card, [{"mask": mask, "kind": "chase", "bytes": int(size),
-                               "iters": iters}],
-                       launches=launches, seed=seed, timeout=timeout, spawn=spawn)
-        if not run["ok"]:
-            out.update(ok=False, reason=run["reason"], detail=run["detail"])
-            return out
-        result = run["tenants"][0]
-        if "skipped" in result:
-            out.update(ok=False, reason="insufficient-memory")
-            return out
-        if int(result["checksum"]) != chase_checksum(
-                result["bytes"], result["workgroups"], result["iters"], seed):
-            out["ok"] = False
-            out.setdefault("reason", "bad-checksum")
-        out["profile"].append({
+    return _profile(
+        card, mask, "chase", sizes, lambda size: {"iters": iters},
+        lambda result, seconds: {
             "bytes": result["bytes"], "nodes": result["nodes"],
             "iters": result["iters"], "ns_per_hop": result["ns_per_hop"],
-            "rate": result["rate"],
-            "seconds": statistics.median(l["seconds"] for l in result["launches"])})
-    return out
+            "rate": result["rate"], "seconds": seconds},
+        None, seed, launches=launches, timeout=timeout, spawn=spawn)
 
 
 if __name__ == "__main__":

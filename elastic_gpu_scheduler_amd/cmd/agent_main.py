@@ -171,94 +171,62 @@ def main(argv=None) -> int:
         print(json.dumps(agent.mask_layouts(), indent=2))
         return 0
 
-    if args.co_tenancy_cache is not None and args.co_tenancy is None:
-        print("--co-tenancy-cache needs --co-tenancy", file=sys.stderr)
-        return 2
+    def given(flag: str) -> bool:
+        return getattr(args, flag[2:].replace("-", "_")) not in (None, False)
 
-    if args.co_tenancy_chase is not None and args.co_tenancy is None:
-        print("--co-tenancy-chase needs --co-tenancy", file=sys.stderr)
-        return 2
-    if args.co_tenancy_chase is not None and args.co_tenancy_cache is not None:
-        print("--co-tenancy-chase and --co-tenancy-cache are separate runs",
-              file=sys.stderr)
-        return 2
-
-    if args.co_tenancy_mfma and args.co_tenancy is None:
-        print("--co-tenancy-mfma needs --co-tenancy", file=sys.stderr)
-        return 2
-    for name, other in (("--co-tenancy-cache", args.co_tenancy_cache),
-                        ("--co-tenancy-chase", args.co_tenancy_chase)):
-        if args.co_tenancy_mfma and other is not None:
-            print(f"--co-tenancy-mfma and {name} are separate runs",
-                  file=sys.stderr)
+    # A flag, the flag it needs, and the flags whose runs are separate from its.
+    for flag, needs, apart in (
+            ("--co-tenancy-cache", "--co-tenancy", ()),
+            ("--co-tenancy-chase", "--co-tenancy", ("--co-tenancy-cache",)),
+            ("--co-tenancy-mfma", "--co-tenancy",
+             ("--co-tenancy-cache", "--co-tenancy-chase")),
+            ("--co-tenancy-mfma-form", "--co-tenancy-mfma", ()),
+            ("--co-tenancy-mfma-operands", "--co-tenancy-mfma", ())):
+        if not given(flag):
+            continue
+        if not given(needs):
+            print(f"{flag} needs {needs}", file=sys.stderr)
             return 2
-
-    if args.co_tenancy_mfma_form is not None and not args.co_tenancy_mfma:
-        print("--co-tenancy-mfma-form needs --co-tenancy-mfma", file=sys.stderr)
-        return 2
-    if args.co_tenancy_mfma_operands is not None and not args.co_tenancy_mfma:
-        print("--co-tenancy-mfma-operands needs --co-tenancy-mfma", file=sys.stderr)
-        return 2
-
-    if args.co_tenancy_mfma:
-        from elastic_gpu_scheduler_amd.agent.cotenancy import MFMA_PAIRS
-
-        agent = NodeAgent(args.node or "local", client=None,
-                          prefer_source=args.source)
-        # Handed on only when the flag is given.
-        more = ({} if args.co_tenancy_mfma_operands is None
-                else {"operands": args.co_tenancy_mfma_operands})
-        if args.co_tenancy_mfma_form is not None:
-            # One card and one form after another: never more than two
-            # children at once.
-            print(json.dumps({card: {form: agent.verify_isolation(
-                card, args.co_tenancy, pairs=MFMA_PAIRS, form=form, **more)
-                for form in args.co_tenancy_mfma_form}
-                for card in sorted(agent.mask_layouts())}, indent=2))
-            return 0
-        # One card after another: never more than two children at once.
-        print(json.dumps({card: agent.verify_isolation(
-            card, args.co_tenancy, pairs=MFMA_PAIRS, **more)
-            for card in sorted(agent.mask_layouts())}, indent=2))
-        return 0
-
-    if args.co_tenancy_chase is not None:
-        from elastic_gpu_scheduler_amd.agent.cotenancy import CHASE_PAIRS
-
-        agent = NodeAgent(args.node or "local", client=None,
-                          prefer_source=args.source)
-        # One card and one size after another: never more than two children
-        # at once.
-        print(json.dumps({card: {str(mib): agent.verify_isolation(
-            card, args.co_tenancy, pairs=CHASE_PAIRS,
-            windows={"chase": {"bytes": mib << 20}})
-            for mib in args.co_tenancy_chase}
-            for card in sorted(agent.mask_layouts())}, indent=2))
-        return 0
-
-    if args.co_tenancy_cache is not None:
-        from elastic_gpu_scheduler_amd.agent.cotenancy import (CACHE_PAIRS,
-                                                               cache_passes)
-
-        agent = NodeAgent(args.node or "local", client=None,
-                          prefer_source=args.source)
-        # One card and one size after another: never more than two children
-        # at once. A cache launch is given the bytes of a default stream
-        # launch, so that neither tenant of a pair outlasts the other by far.
-        print(json.dumps({card: {str(mib): agent.verify_isolation(
-            card, args.co_tenancy, pairs=CACHE_PAIRS,
-            windows={"cache": {"bytes": mib << 20,
-                               "passes": cache_passes(mib << 20)}})
-            for mib in args.co_tenancy_cache}
-            for card in sorted(agent.mask_layouts())}, indent=2))
-        return 0
+        for other in apart:
+            if given(other):
+                print(f"{flag} and {other} are separate runs", file=sys.stderr)
+                return 2
 
     if args.co_tenancy is not None:
+        from elastic_gpu_scheduler_amd.agent.cotenancy import (
+            CACHE_PAIRS, CHASE_PAIRS, MFMA_PAIRS, cache_passes)
+
+        # What every report of the run is asked for and, where a flag names
+        # several forms or sizes, what each of them adds, by its label.
+        common, each = {}, None
+        if args.co_tenancy_mfma:
+            common = {"pairs": MFMA_PAIRS}
+            if args.co_tenancy_mfma_operands is not None:
+                common["operands"] = args.co_tenancy_mfma_operands
+            if args.co_tenancy_mfma_form is not None:
+                each = {form: {"form": form} for form in args.co_tenancy_mfma_form}
+        elif args.co_tenancy_chase is not None:
+            common = {"pairs": CHASE_PAIRS}
+            each = {str(mib): {"windows": {"chase": {"bytes": mib << 20}}}
+                    for mib in args.co_tenancy_chase}
+        elif args.co_tenancy_cache is not None:
+            # A cache launch is given the bytes of a default stream launch, so
+            # that neither tenant of a pair outlasts the other by far.
+            common = {"pairs": CACHE_PAIRS}
+            each = {str(mib): {"windows": {"cache": {
+                "bytes": mib << 20, "passes": cache_passes(mib << 20)}}}
+                for mib in args.co_tenancy_cache}
         agent = NodeAgent(args.node or "local", client=None,
                           prefer_source=args.source)
-        # One card after another: never more than two children at once.
-        print(json.dumps({card: agent.verify_isolation(card, args.co_tenancy)
-                          for card in sorted(agent.mask_layouts())}, indent=2))
+
+        def report(card, more):
+            return agent.verify_isolation(card, args.co_tenancy, **common, **more)
+
+        # One card, and one form or size, after another: never more than two
+        # children at once.
+        print(json.dumps({card: report(card, {}) if each is None else {
+            label: report(card, more) for label, more in each.items()}
+            for card in sorted(agent.mask_layouts())}, indent=2))
         return 0
 
     if args.dry_run:

@@ -766,7 +766,46 @@ tenant_mfma_lds_kernel(uint32_t seed32, int iters, unsigned long long* __restric
 
 // ---- host ------------------------------------------------------------------
 
-enum class Kind { kFma, kStream, kCache, kChase, kMfma };
+enum class Kind : int { kFma, kStream, kCache, kChase, kMfma };
+constexpr int kKinds = 5;
+// Per kind: name, workgroups per CU (chase: one, that is one wave per SIMD),
+// whether it reads a buffer filled beforehand, whether it takes form and operands.
+struct KindInfo {
+  const char* name;
+  int groups_per_cu;
+  bool reads, matrix;
+};
+constexpr KindInfo kKindTable[kKinds] = {
+    {"fma", kGroupsPerCu, false, false},   {"stream", kGroupsPerCu, true, false},
+    {"cache", kCacheGroupsPerCu, true, false}, {"chase", 1, true, false},
+    {"mfma", kMfmaGroupsPerCu, false, true}};
+
+// The kernel of an mfma tenant: [operands from LDS][form].
+using MfmaKernel = decltype(&tenant_mfma_kernel<kBf16>);
+constexpr MfmaKernel kMfmaKernels[2][kMfmaForms] = {
+    {tenant_mfma_kernel<kBf16>, tenant_mfma_kernel<kFp8>, tenant_mfma_kernel<kMxfp8>,
+     tenant_mfma_kernel<kMxfp4>},
+    {tenant_mfma_lds_kernel<kBf16>, tenant_mfma_lds_kernel<kFp8>,
+     tenant_mfma_lds_kernel<kMxfp8>, tenant_mfma_lds_kernel<kMxfp4>}};
+
+double median(std::vector<double> v) {
+  std::sort(v.begin(), v.end());
+  const size_t n = v.size();
+  return n % 2 ? v[n / 2] : 0.5 * (v[n / 2 - 1] + v[n / 2]);
+}
+
+// 64-bit words on the host and their copy on the device; none, nothing to copy.
+struct Mirror {
+  std::vector<unsigned long long>& h;
+  DevBuf d;
+  void copy(bool up) {  // up: allocates
+    if (h.empty()) return;
+    if (up) d.alloc(h.size() * sizeof(h[0]));
+    HIP_CHECK(hipMemcpy(up ? d.p : h.data(), up ? h.data() : d.p, h.size() * sizeof(h[0]),
+                        up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
+  }
+  unsigned long long* at(size_t word) const { return d.as<unsigned long long>() + word; }
+};
 
 struct Launch {
   unsigned long long t0 = 0, t1 = 0;
@@ -795,7 +834,205 @@ struct TenantResult {
   double ns_per_hop = 0.0;  // chase only: median over launches
   double clock_ghz = 0.0;   // mfma only: median over launches
   uint64_t checksum = 0;
+  // Raw: the last launch's word per lane (fma: none), the stamps, mfma's clocks.
+  std::vector<unsigned long long> out, recs, clks;
 };
+
+// Plan: what a call launches, from its arguments alone (no HIP call). The grid
+// depends on the card, never on the mask: the same work either way. (To a
+// process started under ROC_GLOBAL_CU_MASK the runtime reports only that mask's
+// CUs, so there the grid is 32 x its own CUs; every rate is over the work launched.)
+TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int passes,
+                         int form, bool lds) {
+  TenantResult r;
+  r.kind = kind;
+  r.form = form;
+  r.lds = lds;
+  r.workgroups = kKindTable[static_cast<int>(kind)].groups_per_cu * cus;
+  const double lanes = static_cast<double>(r.workgroups) * kBlock;
+  const uint64_t waves = static_cast<uint64_t>(r.workgroups) * kWavesPerGroup;
+  switch (kind) {
+    case Kind::kFma:
+      if (iters <= 0) iters = 65536;
+      r.iters = std::min(iters, 1 << 18);
+      r.work_per_launch = 2.0 * kFmaChains * lanes * r.iters;
+      break;
+    case Kind::kStream:
+    case Kind::kCache: {
+      const bool cache = kind == Kind::kCache;
+      if (bytes == 0) bytes = cache ? 16 * kMiB : kGiB;
+      bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, 16), cache ? kGiB : 16 * kGiB);
+      r.bytes = bytes & ~static_cast<uint64_t>(15);
+      if (passes <= 0) passes = cache ? 1023 : 127;
+      passes = std::min(passes, cache ? 65535 : 4095);
+      r.passes = passes | 1;  // odd: the XOR over all passes is that of one
+      r.work_per_launch = static_cast<double>(r.bytes) * r.passes;
+      if (cache) r.bytes_per_cu = static_cast<double>(r.bytes) / cus;
+      break;
+    }
+    case Kind::kChase:
+      if (bytes == 0) bytes = kGiB;
+      bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, kNodeBytes), 16 * kGiB);
+      r.bytes = bytes & ~(kNodeBytes - 1);
+      r.nodes = r.bytes / kNodeBytes;
+      r.stride = chase_stride(r.nodes);
+      if (iters <= 0) iters = 65536;
+      r.iters = std::min(iters, kMaxChaseIters);  // hops per wave and launch
+      r.work_per_launch = static_cast<double>(waves) * r.iters;
+      break;
+    case Kind::kMfma:
+      if (iters <= 0) iters = kMfmaFormTable[form].default_iters;
+      r.iters = std::min(iters, kMaxMfmaIters);  // steps of four MFMAs per wave and launch
+      r.work_per_launch = static_cast<double>(waves) * r.iters * 4.0 * kMfmaFlopsPerK *
+                          kMfmaFormTable[form].k;
+      if (lds) {
+        r.lds_bytes = static_cast<uint64_t>(kMfmaLdsSlots) * kMfmaLdsStepBytes[form];
+        r.lds_bytes_per_launch = waves * r.iters * kMfmaLdsStepBytes[form];
+      }
+      break;
+  }
+  return r;
+}
+
+// Run: buffers, stream, fill, one untimed launch and `launches` timed ones;
+// leaves r's raw words, the launches' event_seconds and the stream's mask.
+void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
+                 uint64_t seed) {
+  const dim3 grid(r.workgroups);
+  const size_t lanes = static_cast<size_t>(r.workgroups) * kBlock;
+  const uint64_t n16 = r.bytes / 16;
+  DevBuf buf, out;
+  Mirror recs{r.recs}, clks{r.clks};
+  // One record {~0, 0} per timed launch, and one more for the warm-up.
+  recs.h.assign(2 * static_cast<size_t>(launches + 1), 0ULL);
+  for (size_t i = 0; i < recs.h.size(); i += 2) recs.h[i] = ~0ULL;
+  if (kKindTable[static_cast<int>(r.kind)].reads) buf.alloc(r.bytes);
+  switch (r.kind) {  // what a lane stores, and what else a launch records
+    case Kind::kFma:
+      out.alloc(lanes * sizeof(float));
+      break;
+    case Kind::kMfma:  // {sum of shader cycles, sum of wall ticks}, from zero
+      clks.h.assign(recs.h.size(), 0ULL);
+      [[fallthrough]];
+    default:
+      r.out.resize(lanes);
+      out.alloc(lanes * sizeof(unsigned long long));
+  }
+  recs.copy(true);
+  clks.copy(true);
+  HIP_CHECK(hipDeviceSynchronize());
+  std::vector<EventGuard> ev(2 * static_cast<size_t>(launches));
+  for (auto& e : ev) e.create();
+  {
+    StreamGuard g;
+    gpuprobe::open_stream(g, mask, r.applied);
+    const auto go = [&](dim3 blocks, auto kernel, auto... args) {
+      hipLaunchKernelGGL(kernel, blocks, dim3(kBlock), 0, g.s, args...);
+      HIP_CHECK(hipGetLastError());
+    };
+    unsigned long long* const o64 = out.as<unsigned long long>();
+    const auto launch = [&](int slot) {
+      unsigned long long* rec = recs.at(2 * slot);
+      switch (r.kind) {
+        case Kind::kFma:
+          go(grid, tenant_fma_kernel, out.as<float>(), r.iters, 0.999f, 0.001f, rec);
+          break;
+        case Kind::kStream:
+        case Kind::kCache:
+          go(grid, r.kind == Kind::kCache ? tenant_cache_kernel : tenant_stream_kernel,
+             buf.as<const u64x2>(), n16, r.passes, o64, rec);
+          break;
+        case Kind::kChase:
+          go(grid, tenant_chase_kernel, buf.as<const unsigned long long>(), r.nodes,
+             seed % r.nodes, r.iters, o64, rec);
+          break;
+        case Kind::kMfma:
+          go(grid, kMfmaKernels[r.lds][r.form], static_cast<uint32_t>(seed), r.iters, o64,
+             rec, clks.at(2 * slot));
+          break;
+      }
+    };
+    switch (r.kind) {  // the fill
+      case Kind::kStream:
+      case Kind::kCache:
+        go(grid, tenant_fill_kernel, buf.as<ulonglong2>(), n16, seed);
+        break;
+      case Kind::kChase:
+        go(dim3(kGroupsPerCu * cus), tenant_chase_fill_kernel, buf.as<ulonglong2>(), n16,
+           r.nodes, r.stride);
+        break;
+      default:
+        break;
+    }
+    // Warm-up, not timed: the same launch once, so that the code object is
+    // loaded and the clocks have settled under this load before the timed ones.
+    launch(launches);
+    for (int l = 0; l < launches; ++l) {
+      HIP_CHECK(hipEventRecord(ev[2 * l].e, g.s));
+      launch(l);
+      HIP_CHECK(hipEventRecord(ev[2 * l + 1].e, g.s));
+    }
+    HIP_CHECK(hipStreamSynchronize(g.s));
+    recs.copy(false);
+    clks.copy(false);
+    if (!r.out.empty())
+      HIP_CHECK(hipMemcpy(r.out.data(), out.p, lanes * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost));
+  }  // the stream is gone before the result is looked at
+  r.launches.resize(launches);
+  for (int l = 0; l < launches; ++l) {
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * l].e, ev[2 * l + 1].e));
+    r.launches[l].event_seconds = static_cast<double>(ms) * 1e-3;
+  }
+}
+
+// Summarise: launch entries, medians, the last launch's checksum. No HIP call.
+void summarise(TenantResult& r) {
+  std::vector<double> rates, own;
+  for (size_t l = 0; l < r.launches.size(); ++l) {
+    Launch& e = r.launches[l];
+    e.t0 = r.recs[2 * l];
+    e.t1 = r.recs[2 * l + 1];
+    if (e.t0 == ~0ULL || e.t1 <= e.t0)
+      throw std::runtime_error("cu_tenant_run: launch " + std::to_string(l) +
+                               " left no usable clock record");
+    e.seconds = static_cast<double>(e.t1 - e.t0) / r.tick_hz;
+    e.rate = r.work_per_launch / e.seconds / 1e9;
+    rates.push_back(e.rate);
+  }
+  r.rate = median(rates);
+  switch (r.kind) {
+    case Kind::kFma:
+      break;
+    case Kind::kStream:
+    case Kind::kCache:
+      for (unsigned long long w : r.out) r.checksum ^= w;
+      break;
+    case Kind::kChase:
+      // Every lane's end node weighted by its global index, both from 1 so
+      // that neither lane 0 nor node 0 drops out.
+      for (size_t g = 0; g < r.out.size(); ++g) r.checksum += (g + 1) * (r.out[g] + 1);
+      for (const auto& e : r.launches) own.push_back(e.seconds * 1e9 / r.iters);
+      r.ns_per_hop = median(own);
+      break;
+    case Kind::kMfma:  // every lane's fold weighted likewise
+      for (size_t g = 0; g < r.out.size(); ++g) r.checksum += (g + 1) * r.out[g];
+      for (size_t l = 0; l < r.launches.size(); ++l) {
+        Launch& e = r.launches[l];
+        e.cycles = r.clks[2 * l];
+        e.ticks = r.clks[2 * l + 1];
+        if (e.ticks == 0)
+          throw std::runtime_error("cu_tenant_run: launch " + std::to_string(l) +
+                                   " left no usable cycle record");
+        e.clock_ghz = static_cast<double>(e.cycles) / static_cast<double>(e.ticks) *
+                      r.tick_hz / 1e9;
+        own.push_back(e.clock_ghz);
+      }
+      r.clock_ghz = median(own);
+      break;
+  }
+}
 
 TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int launches,
                         int iters, uint64_t bytes, int passes, uint64_t seed, int form,
@@ -805,63 +1042,8 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
   const MaskWords mask =
       raw_mask.empty() ? MaskWords{} : gpuprobe::fit_mask(raw_mask, cus);
   launches = std::min(std::max(launches, 1), kMaxLaunches);
-  // The grid depends on the card, never on the mask given here: the same work
-  // either way. (To a process started under ROC_GLOBAL_CU_MASK the runtime
-  // reports only the CUs of that mask as the card's, so there the grid is 32 x
-  // the process's own CUs; every rate is over the work actually launched.)
-  const bool mfma = kind == Kind::kMfma;
-  const bool reads = kind != Kind::kFma && !mfma;
-  const bool chase = kind == Kind::kChase;
-  // "chase": one workgroup per CU, that is one wave per SIMD.
-  const int grid = (chase  ? 1
-                    : mfma ? kMfmaGroupsPerCu
-                    : kind == Kind::kCache ? kCacheGroupsPerCu
-                                           : kGroupsPerCu) *
-                   cus;
-  const size_t lanes = static_cast<size_t>(grid) * kBlock;
-
-  TenantResult r;
-  r.kind = kind;
-  r.workgroups = grid;
-  if (kind == Kind::kFma) {
-    if (iters <= 0) iters = 65536;
-    r.iters = std::min(iters, 1 << 18);
-    r.work_per_launch = 2.0 * kFmaChains * static_cast<double>(lanes) * r.iters;
-  } else if (mfma) {
-    r.form = form;
-    if (iters <= 0) iters = kMfmaFormTable[form].default_iters;
-    r.iters = std::min(iters, kMaxMfmaIters);  // steps of four MFMAs per wave and launch
-    r.work_per_launch = static_cast<double>(grid) * kWavesPerGroup *
-                        static_cast<double>(r.iters) * 4.0 * kMfmaFlopsPerK *
-                        kMfmaFormTable[form].k;
-    r.lds = lds;
-    if (lds) {
-      r.lds_bytes = static_cast<uint64_t>(kMfmaLdsSlots) * kMfmaLdsStepBytes[form];
-      r.lds_bytes_per_launch = static_cast<uint64_t>(grid) * kWavesPerGroup *
-                               static_cast<uint64_t>(r.iters) * kMfmaLdsStepBytes[form];
-    }
-  } else {
-    const bool cache = kind == Kind::kCache;
-    if (chase) {
-      if (bytes == 0) bytes = kGiB;
-      bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, kNodeBytes), 16 * kGiB);
-      r.bytes = bytes & ~(kNodeBytes - 1);
-      r.nodes = r.bytes / kNodeBytes;
-      r.stride = chase_stride(r.nodes);
-      if (iters <= 0) iters = 65536;
-      r.iters = std::min(iters, kMaxChaseIters);  // hops per wave and launch
-      r.work_per_launch =
-          static_cast<double>(grid) * kWavesPerGroup * static_cast<double>(r.iters);
-    } else {
-      if (bytes == 0) bytes = cache ? 16 * kMiB : kGiB;
-      bytes = std::min<uint64_t>(std::max<uint64_t>(bytes, 16), cache ? kGiB : 16 * kGiB);
-      r.bytes = bytes & ~static_cast<uint64_t>(15);
-      if (passes <= 0) passes = cache ? 1023 : 127;
-      passes = std::min(passes, cache ? 65535 : 4095);
-      r.passes = passes | 1;  // odd: the XOR over all passes is that of one
-      r.work_per_launch = static_cast<double>(r.bytes) * r.passes;
-      if (cache) r.bytes_per_cu = static_cast<double>(r.bytes) / cus;
-    }
+  TenantResult r = plan_tenant(kind, cus, iters, bytes, passes, form, lds);
+  if (kKindTable[static_cast<int>(kind)].reads) {
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     r.free_bytes = free_b;
@@ -875,148 +1057,8 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
   if (clock_khz <= 0)
     throw std::runtime_error("cu_tenant_run: device reports no wall-clock rate");
   r.tick_hz = static_cast<double>(clock_khz) * 1e3;
-
-  const uint64_t n16 = r.bytes / 16;
-  DevBuf buf, out, recs;
-  if (reads) buf.alloc(r.bytes);
-  out.alloc(lanes * (kind == Kind::kFma ? sizeof(float) : sizeof(unsigned long long)));
-  // One record per timed launch, and one more for the warm-up.
-  std::vector<unsigned long long> h_recs(2 * static_cast<size_t>(launches + 1));
-  for (size_t i = 0; i < h_recs.size(); i += 2) {
-    h_recs[i] = ~0ULL;
-    h_recs[i + 1] = 0;
-  }
-  recs.alloc(h_recs.size() * sizeof(unsigned long long));
-  HIP_CHECK(hipMemcpy(recs.p, h_recs.data(), h_recs.size() * sizeof(unsigned long long),
-                      hipMemcpyHostToDevice));
-  // "mfma": {sum of shader cycles, sum of wall ticks} per launch, from zero.
-  DevBuf clks;
-  std::vector<unsigned long long> h_clks(mfma ? h_recs.size() : 0, 0ULL);
-  if (mfma) {
-    clks.alloc(h_clks.size() * sizeof(unsigned long long));
-    HIP_CHECK(hipMemcpy(clks.p, h_clks.data(), h_clks.size() * sizeof(unsigned long long),
-                        hipMemcpyHostToDevice));
-  }
-  HIP_CHECK(hipDeviceSynchronize());
-  std::vector<EventGuard> ev(2 * static_cast<size_t>(launches));
-  for (auto& e : ev) e.create();
-
-  std::vector<unsigned long long> h_out;
-  {
-    StreamGuard g;
-    gpuprobe::open_stream(g, mask, r.applied);
-    const auto mfma_kernel =
-        lds ? (form == kFp8     ? tenant_mfma_lds_kernel<kFp8>
-               : form == kMxfp8 ? tenant_mfma_lds_kernel<kMxfp8>
-               : form == kMxfp4 ? tenant_mfma_lds_kernel<kMxfp4>
-                                : tenant_mfma_lds_kernel<kBf16>)
-            : (form == kFp8     ? tenant_mfma_kernel<kFp8>
-               : form == kMxfp8 ? tenant_mfma_kernel<kMxfp8>
-               : form == kMxfp4 ? tenant_mfma_kernel<kMxfp4>
-                                : tenant_mfma_kernel<kBf16>);
-    auto launch = [&](int slot) {
-      unsigned long long* rec = recs.as<unsigned long long>() + 2 * slot;
-      if (kind == Kind::kFma)
-        hipLaunchKernelGGL(tenant_fma_kernel, dim3(grid), dim3(kBlock), 0, g.s,
-                           out.as<float>(), r.iters, 0.999f, 0.001f, rec);
-      else if (mfma)
-        hipLaunchKernelGGL(mfma_kernel, dim3(grid), dim3(kBlock), 0, g.s,
-                           static_cast<uint32_t>(seed), r.iters,
-                           out.as<unsigned long long>(), rec,
-                           clks.as<unsigned long long>() + 2 * slot);
-      else if (kind == Kind::kStream)
-        hipLaunchKernelGGL(tenant_stream_kernel, dim3(grid), dim3(kBlock), 0, g.s,
-                           buf.as<const u64x2>(), n16, r.passes,
-                           out.as<unsigned long long>(), rec);
-      else if (chase)
-        hipLaunchKernelGGL(tenant_chase_kernel, dim3(grid), dim3(kBlock), 0, g.s,
-                           buf.as<const unsigned long long>(), r.nodes, seed % r.nodes,
-                           r.iters, out.as<unsigned long long>(), rec);
-      else
-        hipLaunchKernelGGL(tenant_cache_kernel, dim3(grid), dim3(kBlock), 0, g.s,
-                           buf.as<const u64x2>(), n16, r.passes,
-                           out.as<unsigned long long>(), rec);
-      HIP_CHECK(hipGetLastError());
-    };
-    if (chase) {
-      hipLaunchKernelGGL(tenant_chase_fill_kernel, dim3(kGroupsPerCu * cus), dim3(kBlock),
-                         0, g.s, buf.as<ulonglong2>(), n16, r.nodes, r.stride);
-      HIP_CHECK(hipGetLastError());
-    } else if (reads) {
-      hipLaunchKernelGGL(tenant_fill_kernel, dim3(grid), dim3(kBlock), 0, g.s,
-                         buf.as<ulonglong2>(), n16, seed);
-      HIP_CHECK(hipGetLastError());
-    }
-    // Warm-up, not timed: the same launch once, so that the code object is
-    // loaded and the clocks have settled under this load before the timed ones.
-    launch(launches);
-    for (int l = 0; l < launches; ++l) {
-      HIP_CHECK(hipEventRecord(ev[2 * l].e, g.s));
-      launch(l);
-      HIP_CHECK(hipEventRecord(ev[2 * l + 1].e, g.s));
-    }
-    HIP_CHECK(hipStreamSynchronize(g.s));
-    HIP_CHECK(hipMemcpy(h_recs.data(), recs.p, h_recs.size() * sizeof(unsigned long long),
-                        hipMemcpyDeviceToHost));
-    if (mfma)
-      HIP_CHECK(hipMemcpy(h_clks.data(), clks.p, h_clks.size() * sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost));
-    if (reads || mfma) {
-      h_out.resize(lanes);
-      HIP_CHECK(hipMemcpy(h_out.data(), out.p, lanes * sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost));
-    }
-  }  // the stream is gone before the result is looked at
-
-  // Of the last launch. "chase": every lane's end node weighted by its global
-  // index, both from 1 so that neither lane 0 nor node 0 drops out.
-  // "mfma": every lane's fold weighted likewise.
-  if (chase)
-    for (size_t g = 0; g < h_out.size(); ++g) r.checksum += (g + 1) * (h_out[g] + 1);
-  else if (mfma)
-    for (size_t g = 0; g < h_out.size(); ++g) r.checksum += (g + 1) * h_out[g];
-  else
-    for (unsigned long long w : h_out) r.checksum ^= w;
-  std::vector<double> rates;
-  for (int l = 0; l < launches; ++l) {
-    Launch e;
-    e.t0 = h_recs[2 * l];
-    e.t1 = h_recs[2 * l + 1];
-    if (e.t0 == ~0ULL || e.t1 <= e.t0)
-      throw std::runtime_error("cu_tenant_run: launch " + std::to_string(l) +
-                               " left no usable clock record");
-    e.seconds = static_cast<double>(e.t1 - e.t0) / r.tick_hz;
-    float ms = 0.0f;
-    HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * l].e, ev[2 * l + 1].e));
-    e.event_seconds = static_cast<double>(ms) * 1e-3;
-    e.rate = r.work_per_launch / e.seconds / 1e9;
-    if (mfma) {
-      e.cycles = h_clks[2 * l];
-      e.ticks = h_clks[2 * l + 1];
-      if (e.ticks == 0)
-        throw std::runtime_error("cu_tenant_run: launch " + std::to_string(l) +
-                                 " left no usable cycle record");
-      e.clock_ghz = static_cast<double>(e.cycles) / static_cast<double>(e.ticks) *
-                    r.tick_hz / 1e9;
-    }
-    rates.push_back(e.rate);
-    r.launches.push_back(e);
-  }
-  std::sort(rates.begin(), rates.end());
-  const size_t n = rates.size();
-  r.rate = n % 2 ? rates[n / 2] : 0.5 * (rates[n / 2 - 1] + rates[n / 2]);
-  if (chase) {
-    std::vector<double> ns;
-    for (const auto& e : r.launches) ns.push_back(e.seconds * 1e9 / r.iters);
-    std::sort(ns.begin(), ns.end());
-    r.ns_per_hop = n % 2 ? ns[n / 2] : 0.5 * (ns[n / 2 - 1] + ns[n / 2]);
-  }
-  if (mfma) {
-    std::vector<double> ghz;
-    for (const auto& e : r.launches) ghz.push_back(e.clock_ghz);
-    std::sort(ghz.begin(), ghz.end());
-    r.clock_ghz = n % 2 ? ghz[n / 2] : 0.5 * (ghz[n / 2 - 1] + ghz[n / 2]);
-  }
+  run_planned(r, cus, mask, launches, seed);
+  summarise(r);
   return r;
 }
 
@@ -1029,18 +1071,9 @@ void register_cotenant(py::module_& m) {
          uint64_t bytes, int passes, uint64_t seed, const std::string& form,
          const std::string& operands) {
         const MaskWords words = gpuprobe::mask_from_python(mask);
-        Kind k;
-        if (kind == "fma")
-          k = Kind::kFma;
-        else if (kind == "stream")
-          k = Kind::kStream;
-        else if (kind == "cache")
-          k = Kind::kCache;
-        else if (kind == "chase")
-          k = Kind::kChase;
-        else if (kind == "mfma")
-          k = Kind::kMfma;
-        else
+        int k = 0;
+        while (k < kKinds && kind != kKindTable[k].name) ++k;
+        if (k == kKinds)
           throw py::value_error(
               "cu_tenant_run: kind must be \"fma\", \"stream\", \"cache\", "
               "\"chase\" or \"mfma\"");
@@ -1049,7 +1082,7 @@ void register_cotenant(py::module_& m) {
         if (f == kMfmaForms)
           throw py::value_error(
               "cu_tenant_run: form must be \"bf16\", \"fp8\", \"mxfp8\" or \"mxfp4\"");
-        if (f != kBf16 && k != Kind::kMfma)
+        if (f != kBf16 && !kKindTable[k].matrix)
           throw py::value_error(
               "cu_tenant_run: form \"" + form + "\" needs kind \"mfma\"; of the forms "
               "\"bf16\", \"fp8\", \"mxfp8\" and \"mxfp4\" every other kind takes only "
@@ -1058,14 +1091,15 @@ void register_cotenant(py::module_& m) {
           throw py::value_error(
               "cu_tenant_run: operands must be \"registers\" or \"lds\"");
         const bool lds = operands == "lds";
-        if (lds && k != Kind::kMfma)
+        if (lds && !kKindTable[k].matrix)
           throw py::value_error(
               "cu_tenant_run: operands \"lds\" needs kind \"mfma\"; of the operands "
               "\"registers\" and \"lds\" every other kind takes only \"registers\"");
         TenantResult r;
         {
           py::gil_scoped_release release;
-          r = run_tenant(device, words, k, launches, iters, bytes, passes, seed, f, lds);
+          r = run_tenant(device, words, static_cast<Kind>(k), launches, iters, bytes,
+                         passes, seed, f, lds);
         }
         py::dict d;
         if (r.skipped) {
@@ -1078,28 +1112,40 @@ void register_cotenant(py::module_& m) {
         d["applied_mask"] = gpuprobe::mask_to_python(r.applied);
         d["tick_hz"] = r.tick_hz;
         d["workgroups"] = r.workgroups;
-        if (k == Kind::kFma) {
-          d["iters"] = r.iters;
-        } else if (k == Kind::kMfma) {
-          d["form"] = kMfmaFormTable[r.form].name;
-          d["iters"] = r.iters;
-          d["checksum"] = r.checksum;
-          if (r.lds) {
-            d["operands"] = operands;
-            d["lds_bytes"] = r.lds_bytes;
-            d["lds_bytes_per_launch"] = r.lds_bytes_per_launch;
-          }
-        } else if (k == Kind::kChase) {
-          d["bytes"] = r.bytes;
-          d["nodes"] = r.nodes;
-          d["stride"] = r.stride;
-          d["iters"] = r.iters;
-          d["checksum"] = r.checksum;
-        } else {
-          d["bytes"] = r.bytes;
-          d["passes"] = r.passes;
-          d["checksum"] = r.checksum;
-          if (k == Kind::kCache) d["bytes_per_cu"] = r.bytes_per_cu;
+        // The kind's keys, whether a launch has clocks, what follows the rate.
+        py::dict last;
+        bool clocks = false;
+        switch (r.kind) {
+          case Kind::kFma:
+            d["iters"] = r.iters;
+            break;
+          case Kind::kStream:
+          case Kind::kCache:
+            d["bytes"] = r.bytes;
+            d["passes"] = r.passes;
+            d["checksum"] = r.checksum;
+            if (r.kind == Kind::kCache) d["bytes_per_cu"] = r.bytes_per_cu;
+            break;
+          case Kind::kChase:
+            d["bytes"] = r.bytes;
+            d["nodes"] = r.nodes;
+            d["stride"] = r.stride;
+            d["iters"] = r.iters;
+            d["checksum"] = r.checksum;
+            last["ns_per_hop"] = r.ns_per_hop;
+            break;
+          case Kind::kMfma:
+            d["form"] = kMfmaFormTable[r.form].name;
+            d["iters"] = r.iters;
+            d["checksum"] = r.checksum;
+            if (r.lds) {
+              d["operands"] = operands;
+              d["lds_bytes"] = r.lds_bytes;
+              d["lds_bytes_per_launch"] = r.lds_bytes_per_launch;
+            }
+            clocks = true;
+            last["clock_ghz"] = r.clock_ghz;
+            break;
         }
         d["work_per_launch"] = r.work_per_launch;
         py::list launches_out;
@@ -1110,7 +1156,7 @@ void register_cotenant(py::module_& m) {
           l["seconds"] = e.seconds;
           l["event_seconds"] = e.event_seconds;
           l["rate"] = e.rate;
-          if (k == Kind::kMfma) {
+          if (clocks) {
             l["cycles"] = e.cycles;
             l["ticks"] = e.ticks;
             l["clock_ghz"] = e.clock_ghz;
@@ -1119,8 +1165,7 @@ void register_cotenant(py::module_& m) {
         }
         d["launches"] = launches_out;
         d["rate"] = r.rate;
-        if (k == Kind::kChase) d["ns_per_hop"] = r.ns_per_hop;
-        if (k == Kind::kMfma) d["clock_ghz"] = r.clock_ghz;
+        d.attr("update")(last);
         return d;
       },
       py::arg("device") = 0, py::arg("mask") = py::none(), py::arg("kind") = "fma",
