@@ -463,6 +463,12 @@ class NodeAgent:
         tenants take their operands from: "lds" makes them re-read every
         step's operands from LDS, as a GEMM does, in place of keeping them
         in registers; their entries then add "operands".
+        pairs=cotenancy.GEMM_PAIRS (gemm/gemm, gemm/stream, stream/gemm,
+        gemm/fma) brings in the sixth kind, a whole bf16 GEMM whose operands
+        travel global memory -> LDS -> MFMA, with a window of bytes (A plus
+        B), iters (steps of 64 k) and passes (GEMMs per launch); its entries
+        carry the clock and its split as the mfma kind's do, and it takes
+        neither form nor operands.
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched

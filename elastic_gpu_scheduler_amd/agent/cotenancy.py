@@ -40,6 +40,18 @@ for the whole launch, or "lds", re-read from the workgroup's LDS before every
 step as a GEMM re-reads its own, the slot rotating with the step. The LDS is
 a CU's, so a mask isolates it fully; the clock it helps to pull down is not.
 
+A sixth kind, "gemm" (GEMM_KINDS, EVERY_KIND, GEMM_PAIRS), is the tenant
+the mfma kind was walked towards: a whole bf16 GEMM whose operands start in
+device memory and travel global -> LDS -> MFMA, the one load that draws on
+the memory path, the LDS and the matrix pipe in one kernel. Its window is
+`bytes` (A plus B), `iters` (steps of 64 k) and `passes` (whole GEMMs per
+launch); gemm_shape() states the shape they give and gemm_checksum() what
+the launch must sum to, in integers and in closed form. Like mfma it
+reports the clock it saw, so a pair splits its ratio the same way: beside
+a streamer both the chip-wide clock and the shared memory path move, and
+cycle_ratio is the part that is not the clock. It takes no form and no
+operands.
+
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
 
@@ -79,6 +91,13 @@ ALL_KINDS = KINDS + MATRIX_KINDS
 # The pairs that say what a neighbour does to a tenant issuing MFMAs.
 MFMA_PAIRS: Tuple[Tuple[str, str], ...] = (
     ("mfma", "mfma"), ("mfma", "stream"), ("stream", "mfma"), ("mfma", "fma"))
+# The kind that is a whole GEMM, operands from memory through LDS to the
+# matrix cores, and every kind including it.
+GEMM_KINDS = ("gemm",)
+EVERY_KIND = ALL_KINDS + GEMM_KINDS
+# The pairs that say what a neighbour does to a tenant running a GEMM.
+GEMM_PAIRS: Tuple[Tuple[str, str], ...] = (
+    ("gemm", "gemm"), ("gemm", "stream"), ("stream", "gemm"), ("gemm", "fma"))
 # What may differ from tenant to tenant, or from kind to kind, within one call.
 WINDOW_KEYS = ("iters", "bytes", "passes")
 # Kinds whose result carries a checksum of the buffer they read.
@@ -351,13 +370,66 @@ def mfma_checksum(workgroups: int, iters: int, seed: int, form: str = "bf16",
     return total * int(iters) % (1 << 64)
 
 
+# --- the gemm tenant's oracle -------------------------------------------------
+
+GEMM_TILE = 128          # rows of A and of B per workgroup
+GEMM_STEP = 64           # k per step: K = 64 * iters
+GEMM_ROW_PERIOD = 192    # A[m][k] and B[n][k] repeat in m and n ...
+GEMM_K_PERIOD = 96       # ... and in k
+
+
+def gemm_shape(bytes: int = 0, iters: int = 0) -> Tuple[int, int, int]:
+    """(m, n, k) of the GEMM a gemm tenant runs for the window keys `bytes`
+    and `iters`, the probe's rule stated on its own: k = 64 * iters (0: 64
+    steps; clamped to 1 .. 512), and m = n = bytes // (4 k), A plus B being
+    4 m k bytes of bf16 (0: 128 MiB), rounded down to a multiple of 128 and
+    clamped to 128 .. 32768."""
+    steps = min(int(iters), 512) if int(iters) > 0 else 64
+    k = GEMM_STEP * steps
+    side = (int(bytes) or 128 << 20) // (4 * k) // GEMM_TILE * GEMM_TILE
+    side = min(max(side, GEMM_TILE), 32768)
+    return side, side, k
+
+
+def gemm_checksum(m: int, n: int, k: int, passes: int, seed: int) -> int:
+    """What a gemm tenant's checksum must be, in integers and closed form. C
+    = A . B^T with A[i][kk] = a(i % 192, kk % 96) and B[j][kk] = b(kk % 96, j
+    % 192), the bf16 hashes of the mfma oracle under key = mix32(seed32 ^
+    0x47454D4D), all in -15 .. 15. Every entry C[i][j] is weighed by (1 + i)
+    (1 + j), and pass p = 0 .. passes - 1 of the launch, each the same
+    product, by 1 + p. With U(r) the sum of 1 + i over the i < m that are r
+    modulo 192, V likewise over n, and cnt(kk) = k // 96 + (kk < k % 96) the
+    k that are kk modulo 96, one GEMM folds to
+
+        G = sum over kk < 96 of cnt(kk) * (sum_r U(r) a(r, kk))
+                                        * (sum_r V(r) b(kk, r)),
+
+    and the checksum is G * passes * (passes + 1) / 2 modulo 2^64: O(m + n +
+    192 * 96) whatever the size."""
+    key = _mix32((int(seed) & _M32) ^ 0x47454D4D)
+
+    def weights(size: int) -> List[int]:
+        out = [0] * GEMM_ROW_PERIOD
+        for i in range(int(size)):
+            out[i % GEMM_ROW_PERIOD] += 1 + i
+        return out
+
+    u, v = weights(m), weights(n)
+    total = 0
+    for kk in range(GEMM_K_PERIOD):
+        cnt = int(k) // GEMM_K_PERIOD + (kk < int(k) % GEMM_K_PERIOD)
+        total += (cnt * sum(u[r] * _mfma_a(key, r, kk) for r in range(GEMM_ROW_PERIOD))
+                  * sum(v[r] * _mfma_b(key, kk, r) for r in range(GEMM_ROW_PERIOD)))
+    return total * (int(passes) * (int(passes) + 1) // 2) % (1 << 64)
+
+
 # --- child ------------------------------------------------------------------
 
 def _child_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="cotenancy", description=__doc__)
     p.add_argument("--child", action="store_true", required=True)
     p.add_argument("--device", type=int, default=0)
-    p.add_argument("--kind", choices=ALL_KINDS, default="fma")
+    p.add_argument("--kind", choices=EVERY_KIND, default="fma")
     p.add_argument("--launches", type=int, default=8)
     p.add_argument("--iters", type=int, default=0)
     p.add_argument("--bytes", type=int, default=0)
@@ -485,7 +557,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
              operands: Optional[str] = None) -> Dict[str, Any]:
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
-    "fma" | "stream" | "cache" | "chase" | "mfma"} and may carry its own "launches", "iters",
+    "fma" | "stream" | "cache" | "chase" | "mfma" | "gemm"} and may carry its own "launches", "iters",
     "bytes" and "passes" in place of the call-wide ones; `kinds`, when given,
     names the kinds instead. Every child warms up and says READY; only then
     are all told GO. Returns {"ok": True, "tenants": [the children's
@@ -502,7 +574,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     carry its own "operands" instead, an unknown value or "operands" on a
     tenant of another kind raises ValueError before anything is started,
     and a child is given --operands, after --form, only when one was named
-    for it.
+    for it. A gemm tenant is of another kind in this sense: it takes
+    neither.
 
     Each child has `timeout` seconds from its start. The first child that
     times out, exits non-zero or prints no TENANT line ends the run: the
@@ -528,7 +601,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     try:
         for i, tenant in enumerate(tenants):
             kind = kinds[i] if kinds is not None else tenant["kind"]
-            if kind not in ALL_KINDS:
+            if kind not in EVERY_KIND:
                 raise ValueError(f"unknown tenant kind {kind!r}")
             env = dict(os.environ)
             env[ENV_CU_MASK] = mask_hex(int(tenant["mask"]))
@@ -599,7 +672,7 @@ def _balanced(launches: int, seconds: Sequence[float]) -> List[int]:
 
 # What a report knows of each kind. First the keys of a child's result that a
 # solo entry adds; a kind that adds clock_ghz gets the clock split in a pair.
-_SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",)}
+_SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",), "gemm": ("clock_ghz",)}
 
 
 def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
@@ -614,6 +687,8 @@ def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
     if kind in MATRIX_KINDS:
         return mfma_checksum(result["workgroups"], result["iters"], seed,
                              form or MFMA_FORMS[0], operands or MFMA_OPERANDS[0])
+    if kind in GEMM_KINDS:
+        return gemm_checksum(result["m"], result["n"], result["k"], result["passes"], seed)
     return None
 
 
@@ -662,6 +737,14 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     cycle_ratio the part that it does not: a tenant slowed only by the
     neighbour's effect on the clock has cycle_ratio 1.
 
+    A gemm tenant (pairs=GEMM_PAIRS) takes `bytes` (A plus B), `iters`
+    (steps of 64 k) and `passes` (whole GEMMs per launch), see gemm_shape();
+    its rates are GFLOP/s and its checksum is held against gemm_checksum().
+    Its entries carry the clock and its split exactly as an mfma tenant's
+    do: beside a streamer clock_ratio is what the chip-wide clock took and
+    cycle_ratio what the shared memory path took. It takes neither `form`
+    nor `operands`; one on a gemm tenant raises ValueError.
+
     `form` (one of MFMA_FORMS, anything else raises ValueError) is the
     instruction the mfma tenants issue, alone and in every pair; a tenant
     ({"mask": int, "form": str}) may name its own instead, for a bf16 tenant
@@ -681,8 +764,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     in registers, and no entry has "operands".
 
     ok says that the measurement is valid (every child exited 0, every
-    stream and cache checksum equals the pattern's, every chase and mfma
-    checksum the closed form's, overlap was reached), not that the
+    stream and cache checksum equals the pattern's, every chase, mfma and
+    gemm checksum the closed form's, overlap was reached), not that the
     tenants are isolated: no interference threshold is built in, on ratio,
     clock_ratio or cycle_ratio. The first
     child that fails ends the report ("child-failed"): nothing further is
@@ -690,11 +773,11 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     if len(tenants) != 2:
         raise ValueError("isolation_report takes two tenants")
     for pair in pairs:
-        if len(pair) != 2 or any(k not in ALL_KINDS for k in pair):
+        if len(pair) != 2 or any(k not in EVERY_KIND for k in pair):
             raise ValueError(f"not a pair of tenant kinds: {pair!r}")
     windows = {kind: dict(w) for kind, w in (windows or {}).items()}
     for kind, w in windows.items():
-        if kind not in ALL_KINDS or any(k not in WINDOW_KEYS for k in w):
+        if kind not in EVERY_KIND or any(k not in WINDOW_KEYS for k in w):
             raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
     # Per option and tenant, what the tenant is started with as an mfma one.
     named = {key: [_mfma_option(key, t, MATRIX_KINDS[0], wide) for t in tenants]
@@ -730,7 +813,7 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         return None
 
     for i, tenant in enumerate(tenants):
-        for kind in ALL_KINDS:
+        for kind in EVERY_KIND:
             if not any(pair[i] == kind for pair in pairs):
                 continue
             run = run_pair(card, [{"mask": tenant["mask"], "kind": kind,

@@ -26,6 +26,8 @@ processes under disjoint masks, each one's rate alone and next to the other.
 chip's and follows no mask; --co-tenancy-mfma-form runs that tenant with the
 FP8 or block-scaled MX instructions in place of the bf16 one, and
 --co-tenancy-mfma-operands lds with its operands re-read from LDS every step.
+--co-tenancy-gemm does it for the tenant all of those lead up to: a whole
+bf16 GEMM whose operands travel global memory -> LDS -> MFMA.
 """
 from __future__ import annotations
 
@@ -147,6 +149,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "the flag is absent), or lds, re-read from LDS before "
                         "every step as a GEMM or attention kernel re-reads "
                         "its own; combines with --co-tenancy-mfma-form")
+    p.add_argument("--co-tenancy-gemm", action="store_true",
+                   help="with --co-tenancy: instead of the FMA and stream "
+                        "pairs, run a tenant that computes a whole bf16 GEMM, "
+                        "operands from device memory through LDS to the "
+                        "matrix cores, next to another such tenant, next to "
+                        "the 1 GiB streamer (both ways round) and next to an "
+                        "FMA tenant, and print one report per card, each "
+                        "ratio split into clock_ratio and cycle_ratio as for "
+                        "--co-tenancy-mfma; not together with "
+                        "--co-tenancy-cache, --co-tenancy-chase or "
+                        "--co-tenancy-mfma")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -181,7 +194,9 @@ def main(argv=None) -> int:
             ("--co-tenancy-mfma", "--co-tenancy",
              ("--co-tenancy-cache", "--co-tenancy-chase")),
             ("--co-tenancy-mfma-form", "--co-tenancy-mfma", ()),
-            ("--co-tenancy-mfma-operands", "--co-tenancy-mfma", ())):
+            ("--co-tenancy-mfma-operands", "--co-tenancy-mfma", ()),
+            ("--co-tenancy-gemm", "--co-tenancy",
+             ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma"))):
         if not given(flag):
             continue
         if not given(needs):
@@ -194,12 +209,14 @@ def main(argv=None) -> int:
 
     if args.co_tenancy is not None:
         from elastic_gpu_scheduler_amd.agent.cotenancy import (
-            CACHE_PAIRS, CHASE_PAIRS, MFMA_PAIRS, cache_passes)
+            CACHE_PAIRS, CHASE_PAIRS, GEMM_PAIRS, MFMA_PAIRS, cache_passes)
 
         # What every report of the run is asked for and, where a flag names
         # several forms or sizes, what each of them adds, by its label.
         common, each = {}, None
-        if args.co_tenancy_mfma:
+        if args.co_tenancy_gemm:
+            common = {"pairs": GEMM_PAIRS}
+        elif args.co_tenancy_mfma:
             common = {"pairs": MFMA_PAIRS}
             if args.co_tenancy_mfma_operands is not None:
                 common["operands"] = args.co_tenancy_mfma_operands

@@ -274,7 +274,7 @@ using int4v = __attribute__((ext_vector_type(4))) int;
 using int8v = __attribute__((ext_vector_type(8))) int;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-__device__ inline uint32_t mix32(uint32_t x) {
+__host__ __device__ inline uint32_t mix32(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7FEB352Du;
   x ^= x >> 15;
@@ -627,12 +627,10 @@ __device__ inline void mfma_fold(const MfmaTile& acc, uint64_t& fold) {
               static_cast<uint64_t>(1 + reg + 16 * t);
 }
 
-// The lane's store, the end stamp and the workgroup's share of clk.
-__device__ inline void mfma_finish(unsigned long long* __restrict__ out,
-                                   unsigned long long* __restrict__ rec,
-                                   unsigned long long* __restrict__ clk, uint64_t fold,
+// The end stamp and the workgroup's share of clk, after its result store.
+__device__ inline void clocked_end(unsigned long long* __restrict__ rec,
+                                   unsigned long long* __restrict__ clk,
                                    unsigned long long c0, unsigned long long t0) {
-  out[static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x] = fold;
   stamp_end(rec, t0);
   if (threadIdx.x == 0) {
     const unsigned long long c1 = __builtin_amdgcn_s_memtime();
@@ -640,6 +638,15 @@ __device__ inline void mfma_finish(unsigned long long* __restrict__ out,
     atomicAdd(&clk[0], c1 - c0);
     atomicAdd(&clk[1], t1 - t0);
   }
+}
+
+// The lane's store, the end stamp and the workgroup's share of clk.
+__device__ inline void mfma_finish(unsigned long long* __restrict__ out,
+                                   unsigned long long* __restrict__ rec,
+                                   unsigned long long* __restrict__ clk, uint64_t fold,
+                                   unsigned long long c0, unsigned long long t0) {
+  out[static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x] = fold;
+  clocked_end(rec, clk, c0, t0);
 }
 
 template <int F>
@@ -764,12 +771,274 @@ tenant_mfma_lds_kernel(uint32_t seed32, int iters, unsigned long long* __restric
   mfma_finish(out, rec, clk, fold, c0, t0);
 }
 
+// ---- gemm ------------------------------------------------------------------
+
+constexpr int kGemmTile = 128;  // rows of A, and of B (columns of C), per workgroup
+constexpr int kGemmBk = 64;     // k per step
+constexpr int kGemmRowVecs = kGemmBk * 2 / 16;           // 16-byte chunks per slab row: 8
+constexpr int kGemmSlabVecs = kGemmTile * kGemmRowVecs;  // one operand's slab: 16 KiB
+constexpr int kGemmLoads = kGemmSlabVecs / kBlock;       // loads per lane, operand and step: 4
+constexpr uint32_t kGemmRowPeriod = 192, kGemmKPeriod = 96;
+constexpr uint32_t kGemmKeySalt = 0x47454D4Du;
+constexpr int kGemmDefaultIters = 64, kGemmMaxIters = 512;
+constexpr int kGemmMaxSide = 32768;
+constexpr int kGemmDefaultPasses = 16;
+constexpr int kGemmMaxGroups = 1 << 22;
+constexpr uint32_t kXcds = 8;          // consecutive workgroup ids go round them
+constexpr uint32_t kGemmBandRows = 8;  // tile rows an XCD's workgroups share
+
+// The operands of a gemm tenant: `buf` is A (S x K, row-major) followed by B
+// (S x K, row n holding column n of the product's right-hand side), both bf16.
+// A[m][k] = mfma_a_hash(key, m % 192, k % 96) % 31 - 15 and B[n][k] =
+// mfma_b_hash(key, k % 96, n % 192) % 31 - 15. One 16-byte store of eight
+// elements per step, grid-stride; k8 = K / 8 counts the stores of a row and
+// n16 = 2 * S * k8 those of both matrices. Eight elements never straddle the
+// k period, a multiple of 8. All indices are 64-bit and below n16.
+__global__ void __launch_bounds__(kBlock)
+tenant_gemm_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint64_t k8, uint32_t key) {
+  uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+  const uint64_t half = n16 / 2;
+  for (; i < n16; i += stride) {
+    const bool is_b = i >= half;
+    const uint64_t at = is_b ? i - half : i;
+    const uint32_t row = static_cast<uint32_t>((at / k8) % kGemmRowPeriod);
+    const uint32_t k0 = static_cast<uint32_t>((at % k8) * 8 % kGemmKPeriod);
+    short8 v;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) {
+      const uint32_t h = is_b ? mfma_b_hash<kBf16>(key, k0 + j, row)
+                              : mfma_a_hash<kBf16>(key, row, k0 + j);
+      v[j] = to_bf16_bits(static_cast<int>(h % 31u) - 15);
+    }
+    buf[i] = __builtin_bit_cast(int4v, v);
+  }
+}
+
+// Which tile workgroup i of a pass computes, as (tile row) << 16 | (tile
+// column), over side x side tiles (side <= 256). A bijection of 0 .. tiles - 1
+// for every tile count, in two steps.
+// 1. Consecutive workgroup ids go round-robin over the 8 XCDs, so XCD x runs
+//    i = x, x + 8, ...: count(x) = tiles / 8 + (x < tiles % 8) of them. They
+//    are given the consecutive positions j = start(x) + i / 8, start(x) = the
+//    sum of the counts before x. i < tiles makes i / 8 < count(x), so the j of
+//    different XCDs do not meet and together are 0 .. tiles - 1.
+// 2. Position j walks the tiles in bands of 8 tile rows (the last band has
+//    the rows that are left), down a band's column first: 64 positions in a
+//    row are an 8 x 8 block of tiles, which reads 8 row slabs of A and 8 of B
+//    where 64 tiles of one row read 1 and 64. j < tiles keeps the column
+//    below side.
+// The workgroups an XCD has in flight are so neighbours in j and share its L2.
+// With GPUPROBE_GEMM_ROW_MAJOR defined the order is the plain one, tile i at
+// row i / side; it is what the kept order was measured against
+// (profiles/gemm_cotenancy_results.md: about 1 % faster than row-major on the
+// whole card, 0.3 % slower on half of it, both near the run-to-run change;
+// the kernel waits on load latency, not on bandwidth, so the order decides
+// little yet).
+__device__ inline uint32_t gemm_order(uint32_t i, uint32_t tiles, uint32_t side) {
+#ifdef GPUPROBE_GEMM_ROW_MAJOR
+  return (i / side) << 16 | (i % side);
+#else
+  const uint32_t x = i % kXcds, q = tiles / kXcds, rem = tiles % kXcds;
+  const uint32_t j = x * q + min(x, rem) + i / kXcds;
+  const uint32_t band = kGemmBandRows * side;
+  const uint32_t first = j / band * kGemmBandRows;
+  const uint32_t rows = min(side - first, kGemmBandRows);
+  const uint32_t in = j % band;
+  return (first + in % rows) << 16 | (in / rows);
+#endif
+}
+
+// Where 16-byte chunk c (0..7, k = 8c .. 8c + 7) of row `row` of a slab
+// lives, in 16-byte units: the row's 128 bytes are unpadded and its chunks
+// are permuted by an XOR with a key of the row's bits 1, 2 and 3.
+__device__ inline uint32_t gemm_key(uint32_t row) {
+  return (row & 6u) | ((row >> 3) & 1u);
+}
+__device__ inline uint32_t gemm_slot(uint32_t row, uint32_t c) {
+  return row * kGemmRowVecs + (c ^ gemm_key(row));
+}
+
+// A bf16 GEMM whose operands travel global memory -> LDS -> MFMA: C (S x S,
+// f32 accumulators, never stored) = A (S x K) . B^T, B stored S x K, K =
+// 64 x steps, S = 128 x side. The grid is tiles x passes workgroups, tiles =
+// side^2; workgroup g computes tile gemm_order(g % tiles) of pass g / tiles,
+// every pass the same product.
+//
+// Work split. A workgroup owns a 128 x 128 tile of C; its four waves sit 2 x
+// 2 (wave j: rows 64 (j >> 1), columns 64 (j & 1)) and each owns 64 x 64 as
+// an MfmaTile, with the fragment rule of MfmaFrags<kBf16>: lane r + 32 h of
+// fragment t holds row (A) or column (B) 32 t + r at k = 8 h .. 8 h + 7, one
+// 16-byte chunk. One step (64 k) is four sub-steps of four MFMAs; sub-step s
+// uses chunk 2 s + h.
+//
+// Data movement. Per step the workgroup moves a 128 x 64 slab of A and one of
+// B, 16 KiB each, into LDS: lane t loads chunk t & 7 of rows (t >> 3) + 32 i,
+// i = 0..3, of either slab, so eight lanes read the 128 contiguous bytes of a
+// row and a lane has eight 16-byte loads in flight. LDS holds two buffers of
+// {A slab, B slab}, 64 KiB, and 2 KiB for the reduction at the end: two
+// workgroups fit a CU's 160 KiB.
+//
+// LDS layout (gemm_slot): row-major, 128 bytes a row, no padding; chunk c of
+// row R is stored at chunk position c ^ q(R), q(R) = (R & 6) | ((R >> 3) & 1).
+// The 64 banks are 256 bytes, that is two rows, so a 16-byte access falls
+// into bank group (R & 1) * 8 + (c ^ q(R)) of 16, and 16 lanes are served at a
+// time. A fragment read has lane r on row base + r (base a multiple of 32) at
+// one c per h: over 16 consecutive r, (r & 1, q(r)) takes all 16 values, so
+// the 16 lanes fall into 16 different bank groups; and should the hardware
+// pair eight lanes of h = 0 with eight of h = 1 instead, their chunks c and c
+// ^ 1 meet keys q(0..7) = {0, 2, 4, 6} and stay apart too. A slab write has
+// 16 consecutive lanes on rows R, R + 1 (R even) and all eight c: whatever q,
+// each row's eight lanes fill its eight positions. So neither ds_read_b128
+// nor ds_write_b128 has a bank conflict. (With plain 128-byte rows every
+// lane of a fragment read would fall into one of two bank groups.)
+//
+// Pipeline. The slab of step i + 1 is loaded from global memory into
+// registers before the MFMAs of step i are issued and written to the other
+// LDS buffer after them; one workgroup barrier ends the step. That barrier
+// is enough: the buffer written in step i was last read in step i - 1, which
+// every wave left through the barrier before. Within a step the fragment
+// reads of sub-step s + 1 go in front of the first three MFMAs of sub-step s
+// (mfma_lds_interleave, two reads per 32 cycles of MFMA) into a second
+// register set; only sub-step 0's reads, which have to follow the barrier,
+// are not covered by the wave's own MFMAs, and there the CU's other waves
+// issue theirs. The last step loads and writes nothing.
+//
+// Bounds. S and K are multiples of the tile and of the step by construction,
+// so nothing is masked. A global index is (128 tile + row) * K/8 + 8 step +
+// chunk with tile < side, row < 128, step < steps and chunk < 8, below S *
+// K/8, the 16-byte elements of one matrix. An LDS index is gemm_slot of a row
+// below 128 and a chunk below 8, below the slab's 1024.
+//
+// Exactness. Operands are integers of magnitude <= 15, so a product's sum
+// over K <= 32768 stays below 32768 * 225 < 2^23: every accumulator is an
+// exact integer in f32 at every step.
+//
+// Result. Every lane converts its 64 accumulators to integers and weighs the
+// entry at (m, n), global, by (1 + m) (1 + n) modulo 2^64; the 256 sums are
+// added up through LDS and thread 0 stores the workgroup's one word out[g].
+// Stamps and clocks are the mfma kind's (clocked_end). The addresses of the
+// first slab are computed before the start stamp, its loads are inside it;
+// between the stamps nothing but the operand loads and that one store
+// touches global memory.
+//
+// No FP32 arithmetic but the MFMAs' is written here or in the fill, so the
+// compiler has nothing to pack into two-wide FP32 instructions.
+//
+// hipcc -O3 for gfx950 reports (-Rpass-analysis=kernel-resource-usage) 159
+// VGPRs, no AGPRs, 32 SGPRs, no scratch and no spills, 67584 bytes of LDS and
+// an occupancy of 2 waves per SIMD: two workgroups per CU by registers and
+// by LDS alike.
+__global__ void __launch_bounds__(kBlock, 2)
+tenant_gemm_kernel(const int4v* __restrict__ a, const int4v* __restrict__ b, uint32_t side,
+                   uint32_t steps, unsigned long long* __restrict__ out,
+                   unsigned long long* __restrict__ rec,
+                   unsigned long long* __restrict__ clk) {
+  __shared__ int4v slab[2][2][kGemmSlabVecs];  // [buffer][A, B]
+  __shared__ unsigned long long sums[kBlock];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = lane & 31u, h = lane >> 5;
+  const uint32_t wave = threadIdx.x / 64;
+  const uint32_t tiles = side * side;
+  const uint32_t tile = gemm_order(blockIdx.x % tiles, tiles, side);
+  const uint32_t row0 = (tile >> 16) * kGemmTile, col0 = (tile & 0xFFFFu) * kGemmTile;
+  // What this lane loads: chunk threadIdx & 7 of rows (threadIdx >> 3) + 32 i.
+  const uint64_t k8 = static_cast<uint64_t>(steps) * kGemmRowVecs;
+  const uint32_t load_row = threadIdx.x >> 3, load_c = threadIdx.x & 7u;
+  const int4v* pa = a + (row0 + load_row) * k8 + load_c;
+  const int4v* pb = b + (col0 + load_row) * k8 + load_c;
+  const uint64_t load_stride = 32 * k8;                   // 32 rows on
+  const uint32_t write_at = gemm_slot(load_row, load_c);  // + 32 rows: + 256
+  // What this lane reads: rows 64 x (wave's half) + 32 t + r of either slab,
+  // at sub-step s the chunk 2 s + h; 32 t and 64 leave the row's key alone.
+  const uint32_t read_a = (64 * (wave >> 1) + r) * kGemmRowVecs;
+  const uint32_t read_b = (64 * (wave & 1u) + r) * kGemmRowVecs;
+  const uint32_t read_key = gemm_key(r);
+
+  int4v next[2][kGemmLoads];
+  const auto fetch = [&] {
+#pragma unroll
+    for (int i = 0; i < kGemmLoads; ++i) {
+      next[0][i] = pa[i * load_stride];
+      next[1][i] = pb[i * load_stride];
+    }
+    pa += kGemmRowVecs;
+    pb += kGemmRowVecs;
+  };
+  const auto store = [&](int4v (*to)[kGemmSlabVecs]) {
+#pragma unroll
+    for (int i = 0; i < kGemmLoads; ++i) {
+      to[0][write_at + 32 * kGemmRowVecs * i] = next[0][i];
+      to[1][write_at + 32 * kGemmRowVecs * i] = next[1][i];
+    }
+  };
+  const auto read = [&](MfmaFrags<kBf16>& f, const int4v (*from)[kGemmSlabVecs], uint32_t s) {
+    const uint32_t c = (2 * s + h) ^ read_key;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f.a[t] = __builtin_bit_cast(bf16x8, from[0][read_a + 32 * kGemmRowVecs * t + c]);
+      f.b[t] = __builtin_bit_cast(bf16x8, from[1][read_b + 32 * kGemmRowVecs * t + c]);
+    }
+  };
+  f32x16 acc[2][2];
+  // One step's sixteen MFMAs on the slabs of `from`.
+  const auto multiply = [&](const int4v (*from)[kGemmSlabVecs]) {
+    MfmaFrags<kBf16> f[2];
+    read(f[0], from, 0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (uint32_t s = 0; s < 4; ++s) {
+      if (s < 3) read(f[(s + 1) & 1u], from, s + 1);
+      mfma_step(f[s & 1u], acc);
+      if (s < 3) mfma_lds_interleave<4, 2>();
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  const unsigned long long t0 = stamp_start();
+  mfma_zero(acc);
+  fetch();
+  store(slab[0]);
+  __syncthreads();
+  for (uint32_t i = 0; i + 1 < steps; ++i) {
+    fetch();  // step i + 1, in flight under the MFMAs of step i
+    multiply(slab[i & 1u]);
+    store(slab[(i + 1) & 1u]);
+    __syncthreads();
+  }
+  multiply(slab[(steps - 1) & 1u]);
+
+  uint64_t sum = 0;
+#pragma unroll
+  for (uint32_t t = 0; t < 4; ++t) {
+    const uint32_t m = row0 + 64 * (wave >> 1) + 32 * (t >> 1) + 4 * h;
+    const uint32_t n = col0 + 64 * (wave & 1u) + 32 * (t & 1u) + r;
+    uint64_t column = 0;
+#pragma unroll
+    for (uint32_t reg = 0; reg < 16; ++reg)
+      column += static_cast<uint64_t>(static_cast<int64_t>(
+                    static_cast<int>(acc[t >> 1][t & 1][reg]))) *
+                static_cast<uint64_t>(1 + m + (reg & 3u) + 8 * (reg >> 2));
+    sum += column * static_cast<uint64_t>(1 + n);
+  }
+  sums[threadIdx.x] = sum;
+  __syncthreads();
+  for (uint32_t width = kBlock / 2; width > 0; width >>= 1) {
+    if (threadIdx.x < width) sums[threadIdx.x] += sums[threadIdx.x + width];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = sums[0];
+  clocked_end(rec, clk, c0, t0);
+}
+
 // ---- host ------------------------------------------------------------------
 
-enum class Kind : int { kFma, kStream, kCache, kChase, kMfma };
-constexpr int kKinds = 5;
-// Per kind: name, workgroups per CU (chase: one, that is one wave per SIMD),
-// whether it reads a buffer filled beforehand, whether it takes form and operands.
+enum class Kind : int { kFma, kStream, kCache, kChase, kMfma, kGemm };
+constexpr int kKinds = 6;
+// Per kind: name, workgroups per CU (chase: one, that is one wave per SIMD;
+// gemm: none, its grid is the problem's), whether it reads a buffer filled
+// beforehand, whether it takes form and operands.
 struct KindInfo {
   const char* name;
   int groups_per_cu;
@@ -778,7 +1047,7 @@ struct KindInfo {
 constexpr KindInfo kKindTable[kKinds] = {
     {"fma", kGroupsPerCu, false, false},   {"stream", kGroupsPerCu, true, false},
     {"cache", kCacheGroupsPerCu, true, false}, {"chase", 1, true, false},
-    {"mfma", kMfmaGroupsPerCu, false, true}};
+    {"mfma", kMfmaGroupsPerCu, false, true},   {"gemm", 0, true, false}};
 
 // The kernel of an mfma tenant: [operands from LDS][form].
 using MfmaKernel = decltype(&tenant_mfma_kernel<kBf16>);
@@ -810,8 +1079,8 @@ struct Mirror {
 struct Launch {
   unsigned long long t0 = 0, t1 = 0;
   double seconds = 0.0, event_seconds = 0.0, rate = 0.0;
-  unsigned long long cycles = 0, ticks = 0;  // mfma only
-  double clock_ghz = 0.0;                    // mfma only
+  unsigned long long cycles = 0, ticks = 0;  // mfma and gemm only
+  double clock_ghz = 0.0;                    // mfma and gemm only
 };
 
 struct TenantResult {
@@ -827,14 +1096,19 @@ struct TenantResult {
   uint64_t bytes = 0;
   int iters = 0, passes = 0;
   uint64_t nodes = 0, stride = 0;  // chase only
-  double work_per_launch = 0.0;  // flops (fma, mfma), bytes (stream, cache) or hops (chase)
+  int side = 0, tiles = 0;         // gemm only: tiles per side and per pass
+  uint64_t m = 0, n = 0, k = 0;    // gemm only
+  uint64_t load_bytes_per_launch = 0;  // gemm only
+  // flops (fma, mfma, gemm), bytes (stream, cache) or hops (chase)
+  double work_per_launch = 0.0;
   double bytes_per_cu = 0.0;     // cache only
   std::vector<Launch> launches;
   double rate = 0.0;  // median over launches: GFLOP/s, GB/s or Ghop/s
   double ns_per_hop = 0.0;  // chase only: median over launches
-  double clock_ghz = 0.0;   // mfma only: median over launches
+  double clock_ghz = 0.0;   // mfma and gemm only: median over launches
   uint64_t checksum = 0;
-  // Raw: the last launch's word per lane (fma: none), the stamps, mfma's clocks.
+  // Raw: the last launch's word per lane (fma: none; gemm: per workgroup),
+  // the stamps, mfma's and gemm's clocks.
   std::vector<unsigned long long> out, recs, clks;
 };
 
@@ -890,6 +1164,25 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
         r.lds_bytes_per_launch = waves * r.iters * kMfmaLdsStepBytes[form];
       }
       break;
+    case Kind::kGemm: {
+      // agent/cotenancy.py states the same rule on its own (gemm_shape).
+      if (iters <= 0) iters = kGemmDefaultIters;
+      r.iters = std::min(iters, kGemmMaxIters);  // steps of 64 k
+      r.k = static_cast<uint64_t>(kGemmBk) * r.iters;
+      if (bytes == 0) bytes = 128 * kMiB;
+      const uint64_t s = bytes / (4 * r.k) / kGemmTile * kGemmTile;
+      r.m = r.n = std::min<uint64_t>(std::max<uint64_t>(s, kGemmTile), kGemmMaxSide);
+      r.bytes = 4 * r.m * r.k;  // A and B, two bytes an element
+      r.side = static_cast<int>(r.m / kGemmTile);
+      r.tiles = r.side * r.side;
+      if (passes <= 0) passes = kGemmDefaultPasses;
+      r.passes = std::min(passes, kGemmMaxGroups / r.tiles);
+      r.workgroups = r.tiles * r.passes;
+      r.work_per_launch = 2.0 * r.m * r.n * r.k * r.passes;
+      r.load_bytes_per_launch =
+          static_cast<uint64_t>(r.workgroups) * 2 * kGemmTile * r.k * 2;
+      break;
+    }
   }
   return r;
 }
@@ -899,7 +1192,9 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
 void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
                  uint64_t seed) {
   const dim3 grid(r.workgroups);
-  const size_t lanes = static_cast<size_t>(r.workgroups) * kBlock;
+  // What a launch leaves: a word per lane, for gemm one per workgroup.
+  const size_t lanes =
+      static_cast<size_t>(r.workgroups) * (r.kind == Kind::kGemm ? 1 : kBlock);
   const uint64_t n16 = r.bytes / 16;
   DevBuf buf, out;
   Mirror recs{r.recs}, clks{r.clks};
@@ -912,6 +1207,7 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
       out.alloc(lanes * sizeof(float));
       break;
     case Kind::kMfma:  // {sum of shader cycles, sum of wall ticks}, from zero
+    case Kind::kGemm:
       clks.h.assign(recs.h.size(), 0ULL);
       [[fallthrough]];
     default:
@@ -950,6 +1246,11 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
           go(grid, kMfmaKernels[r.lds][r.form], static_cast<uint32_t>(seed), r.iters, o64,
              rec, clks.at(2 * slot));
           break;
+        case Kind::kGemm:  // A, then B behind it
+          go(grid, tenant_gemm_kernel, buf.as<const int4v>(), buf.as<const int4v>() + n16 / 2,
+             static_cast<uint32_t>(r.side), static_cast<uint32_t>(r.iters), o64, rec,
+             clks.at(2 * slot));
+          break;
       }
     };
     switch (r.kind) {  // the fill
@@ -960,6 +1261,10 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
       case Kind::kChase:
         go(dim3(kGroupsPerCu * cus), tenant_chase_fill_kernel, buf.as<ulonglong2>(), n16,
            r.nodes, r.stride);
+        break;
+      case Kind::kGemm:
+        go(dim3(kGroupsPerCu * cus), tenant_gemm_fill_kernel, buf.as<int4v>(), n16, r.k / 8,
+           mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
         break;
       default:
         break;
@@ -1017,7 +1322,9 @@ void summarise(TenantResult& r) {
       r.ns_per_hop = median(own);
       break;
     case Kind::kMfma:  // every lane's fold weighted likewise
-      for (size_t g = 0; g < r.out.size(); ++g) r.checksum += (g + 1) * r.out[g];
+    case Kind::kGemm:  // every workgroup's word weighted by its pass, from 1
+      for (size_t g = 0; g < r.out.size(); ++g)
+        r.checksum += (r.kind == Kind::kGemm ? 1 + g / r.tiles : g + 1) * r.out[g];
       for (size_t l = 0; l < r.launches.size(); ++l) {
         Launch& e = r.launches[l];
         e.cycles = r.clks[2 * l];
@@ -1076,7 +1383,7 @@ void register_cotenant(py::module_& m) {
         if (k == kKinds)
           throw py::value_error(
               "cu_tenant_run: kind must be \"fma\", \"stream\", \"cache\", "
-              "\"chase\" or \"mfma\"");
+              "\"chase\", \"mfma\" or \"gemm\"");
         int f = 0;
         while (f < kMfmaForms && form != kMfmaFormTable[f].name) ++f;
         if (f == kMfmaForms)
@@ -1146,6 +1453,17 @@ void register_cotenant(py::module_& m) {
             clocks = true;
             last["clock_ghz"] = r.clock_ghz;
             break;
+          case Kind::kGemm:
+            d["m"] = r.m;
+            d["n"] = r.n;
+            d["k"] = r.k;
+            d["bytes"] = r.bytes;
+            d["passes"] = r.passes;
+            d["checksum"] = r.checksum;
+            d["load_bytes_per_launch"] = r.load_bytes_per_launch;
+            clocks = true;
+            last["clock_ghz"] = r.clock_ghz;
+            break;
         }
         d["work_per_launch"] = r.work_per_launch;
         py::list launches_out;
@@ -1175,12 +1493,13 @@ void register_cotenant(py::module_& m) {
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
-      "\"cache\", \"chase\" or \"mfma\", anything else raises ValueError "
+      "\"cache\", \"chase\", \"mfma\" or \"gemm\", anything else raises ValueError "
       "before the device is touched. After one untimed "
       "launch, `launches` (1..64) launches of the same work run back to back "
       "on one stream, each between its own pair of events; the grid is 32 x "
       "CUs workgroups of 256 lanes (cache: 8 x CUs, all resident at once; "
-      "chase: 1 x CUs, one wave per SIMD; mfma: 8 x CUs) "
+      "chase: 1 x CUs, one wave per SIMD; mfma: 8 x CUs; gemm: the problem's "
+      "tiles x passes) "
       "whatever `mask` is, CUs being what the device reports to this "
       "process.\n\n"
       "fma: 16 independent FP32 FMA chains of `iters` (default 65536, at most "
@@ -1320,10 +1639,47 @@ void register_cotenant(py::module_& m) {
       "waves * iters * the form's bytes per slot, and its checksum equals "
       "mfma_checksum(..., form, \"lds\"). With \"registers\" the result has "
       "none of the three.\n\n"
+      "gemm: a bf16 GEMM whose operands travel global memory -> LDS -> MFMA, C "
+      "(M x N, f32 accumulators, never stored) = A (M x K, row-major) . B^T "
+      "with B stored N x K, M = N. `iters` is the steps of 64 k, K = 64 * "
+      "iters (default 64: K = 4096; clamped to 1 .. 512); `bytes` is the size "
+      "of A plus B (default 128 MiB), M = bytes // (4 K) rounded down to a "
+      "multiple of 128 and clamped to 128 .. 32768, and the result reports "
+      "the bytes really used, 4 M K (default: M = 8192); `passes` is the "
+      "whole GEMMs of one launch (default 16, clamped to 1 .. 2^22 // tiles). "
+      "Refused like stream. The grid is tiles x passes workgroups, tiles = (M "
+      "/ 128)^2; workgroup g computes, in pass g // tiles, the 128 x 128 tile "
+      "that a fixed bijection gives g % tiles: the workgroups of one XCD "
+      "(ids 8 apart) take consecutive places in a walk over the tiles in "
+      "bands of 8 tile rows, column by column. Its four waves sit 2 x 2, "
+      "each on 64 x 64 as for mfma, and one step is 16 "
+      "v_mfma_f32_32x32x16_bf16 per wave on a 128 x 64 slab of A and one of "
+      "B, 32 KiB, that the workgroup loaded with eight 16-byte loads per "
+      "lane into one of two LDS buffers (rows of 128 bytes whose eight "
+      "16-byte chunks are permuted by an XOR with row bits 1, 2 and 3, so "
+      "that neither the ds_write_b128 of a slab nor the ds_read_b128 of a "
+      "fragment has a bank conflict; 66 KiB of LDS, two workgroups per CU); "
+      "the loads of the next step are in flight under the MFMAs of this one, "
+      "with one barrier per step. Both matrices are written once on the same "
+      "stream before anything is timed: A[m][k] = mix32(key ^ (m % 192) << 8 "
+      "^ (k % 96) ^ 0xA00000) % 31 - 15, B[n][k] = mix32(key ^ (k % 96) << 8 "
+      "^ (n % 192) ^ 0xB00000) % 31 - 15, key = mix32(seed32 ^ 0x47454D4D): "
+      "integers, so every accumulator stays below 32768 * 225 < 2^23 and is "
+      "exact. At the end every lane weighs its entries at (m, n) by (1 + m) "
+      "(1 + n) modulo 2^64, the workgroup adds its lanes up through LDS and "
+      "stores one word; checksum = the sum over g of (1 + g // tiles) * "
+      "word(g) modulo 2^64, equal to agent/cotenancy.py's gemm_checksum only "
+      "when every tile of every pass was computed exactly and once. Clocks "
+      "as for mfma. The result has m, n, k, bytes, passes, checksum, "
+      "load_bytes_per_launch = tiles * passes * 2 * 128 * K * 2, what the "
+      "global loads ask for, work_per_launch = 2 M N K passes flops, rates "
+      "in GFLOP/s, and clock_ghz per launch and as the median. It takes no "
+      "form but \"bf16\" and no operands but \"registers\".\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
-      "{kind, [form,] applied_mask, tick_hz, workgroups, iters | bytes, passes, checksum, "
+      "{kind, [form,] applied_mask, tick_hz, workgroups, iters | [m, n, k,] bytes, passes, "
+      "checksum, [load_bytes_per_launch,] "
       "[operands, lds_bytes, lds_bytes_per_launch,] "
       "[bytes_per_cu,] work_per_launch: flops, bytes or hops, launches: [{t0, t1, "
       "seconds: (t1 - t0) "
