@@ -468,7 +468,10 @@ class NodeAgent:
         travel global memory -> LDS -> MFMA, with a window of bytes (A plus
         B), iters (steps of 64 k) and passes (GEMMs per launch); its entries
         carry the clock and its split as the mfma kind's do, and it takes
-        neither form nor operands.
+        neither form nor operands. pairs=cotenancy.mxgemm_pairs("gemm-mxfp8"
+        | "gemm-mxfp4") puts the block-scaled GEMM in its place, e4m3 or
+        e2m1 elements under E8M0 scales per block of 32 k, steps of 128 or
+        256 k; the form is the kind's name, so these take neither either.
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched

@@ -52,6 +52,14 @@ a streamer both the chip-wide clock and the shared memory path move, and
 cycle_ratio is the part that is not the clock. It takes no form and no
 operands.
 
+Two more kinds, "gemm-mxfp8" and "gemm-mxfp4" (MXGEMM_KINDS, TENANT_KINDS,
+mxgemm_pairs()), are that GEMM in the forms inference tenants run: e4m3 or
+e2m1 elements under one E8M0 scale per row and block of 32 k, the elements
+through LDS, the scales from memory straight to registers, two slabs in
+flight. The form is part of the kind's name, so they too take neither form
+nor operands; their window is the gemm kind's with a step of 128 or 256 k,
+and gemm_shape() and gemm_checksum() take the form as a keyword.
+
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
 
@@ -98,6 +106,19 @@ EVERY_KIND = ALL_KINDS + GEMM_KINDS
 # The pairs that say what a neighbour does to a tenant running a GEMM.
 GEMM_PAIRS: Tuple[Tuple[str, str], ...] = (
     ("gemm", "gemm"), ("gemm", "stream"), ("stream", "gemm"), ("gemm", "fma"))
+# The kinds that are a block-scaled GEMM, the form in the name; every kind
+# there is; and the pairs that say what a neighbour does to such a tenant.
+MXGEMM_KINDS = ("gemm-mxfp8", "gemm-mxfp4")
+TENANT_KINDS = EVERY_KIND + MXGEMM_KINDS
+
+
+def mxgemm_pairs(kind: str) -> Tuple[Tuple[str, str], ...]:
+    """GEMM_PAIRS with `kind` (one of MXGEMM_KINDS) in place of "gemm"."""
+    if kind not in MXGEMM_KINDS:
+        raise ValueError(f"not a block-scaled gemm kind: {kind!r}")
+    return tuple(tuple(kind if k == "gemm" else k for k in pair) for pair in GEMM_PAIRS)
+
+
 # What may differ from tenant to tenant, or from kind to kind, within one call.
 WINDOW_KEYS = ("iters", "bytes", "passes")
 # Kinds whose result carries a checksum of the buffer they read.
@@ -376,22 +397,44 @@ GEMM_TILE = 128          # rows of A and of B per workgroup
 GEMM_STEP = 64           # k per step: K = 64 * iters
 GEMM_ROW_PERIOD = 192    # A[m][k] and B[n][k] repeat in m and n ...
 GEMM_K_PERIOD = 96       # ... and in k
+# Per form of a GEMM tenant ("bf16": the gemm kind; the others: "gemm-" + the
+# form), as in csrc/gpuprobe/cotenant.hip: the k of one step, a slab row of
+# 128 bytes in every form, the most steps whose sums stay exact in f32, and
+# the bytes of a row's scales per step (one E8M0 byte per block of 32 k).
+GEMM_FORM_TABLE: Dict[str, Dict[str, int]] = {
+    "bf16": {"step": 64, "max_iters": 512, "scale_bytes": 0},
+    "mxfp8": {"step": 128, "max_iters": 256, "scale_bytes": 4},
+    "mxfp4": {"step": 256, "max_iters": 64, "scale_bytes": 8},
+}
 
 
-def gemm_shape(bytes: int = 0, iters: int = 0) -> Tuple[int, int, int]:
+def _gemm_form(form: str) -> Dict[str, int]:
+    if form not in GEMM_FORM_TABLE:
+        raise ValueError(f"unknown gemm form {form!r}: one of " + ", ".join(GEMM_FORM_TABLE))
+    return GEMM_FORM_TABLE[form]
+
+
+def gemm_shape(bytes: int = 0, iters: int = 0, form: str = "bf16") -> Tuple[int, int, int]:
     """(m, n, k) of the GEMM a gemm tenant runs for the window keys `bytes`
     and `iters`, the probe's rule stated on its own: k = 64 * iters (0: 64
     steps; clamped to 1 .. 512), and m = n = bytes // (4 k), A plus B being
     4 m k bytes of bf16 (0: 128 MiB), rounded down to a multiple of 128 and
-    clamped to 128 .. 32768."""
-    steps = min(int(iters), 512) if int(iters) > 0 else 64
-    k = GEMM_STEP * steps
-    side = (int(bytes) or 128 << 20) // (4 * k) // GEMM_TILE * GEMM_TILE
+    clamped to 128 .. 32768.
+
+    `form` "mxfp8" or "mxfp4" is the rule of the gemm-mxfp8 and gemm-mxfp4
+    kinds: a step is 128 or 256 k (0: K = 4096; clamped to 1 .. 256 or 1 ..
+    64 steps), and A plus B, the elements alone, are 2 m k or m k bytes, in
+    every form 256 bytes per row and step (0: m = 8192)."""
+    rule = _gemm_form(form)
+    steps = min(int(iters), rule["max_iters"]) if int(iters) > 0 else 4096 // rule["step"]
+    unset = 128 << 20 if form == "bf16" else 8192 * 256 * steps
+    side = (int(bytes) or unset) // (256 * steps) // GEMM_TILE * GEMM_TILE
     side = min(max(side, GEMM_TILE), 32768)
-    return side, side, k
+    return side, side, rule["step"] * steps
 
 
-def gemm_checksum(m: int, n: int, k: int, passes: int, seed: int) -> int:
+def gemm_checksum(m: int, n: int, k: int, passes: int, seed: int,
+                  form: str = "bf16") -> int:
     """What a gemm tenant's checksum must be, in integers and closed form. C
     = A . B^T with A[i][kk] = a(i % 192, kk % 96) and B[j][kk] = b(kk % 96, j
     % 192), the bf16 hashes of the mfma oracle under key = mix32(seed32 ^
@@ -405,7 +448,15 @@ def gemm_checksum(m: int, n: int, k: int, passes: int, seed: int) -> int:
                                         * (sum_r V(r) b(kk, r)),
 
     and the checksum is G * passes * (passes + 1) / 2 modulo 2^64: O(m + n +
-    192 * 96) whatever the size."""
+    192 * 96) whatever the size.
+
+    `form` "mxfp8" or "mxfp4" takes a and b from the hashes of that form,
+    each element under the scale of its own block of 32 k, block (kk % 96)
+    // 32 of the three in a k period: the effective integers of the mfma
+    oracle, |a| <= 14 and |b| <= 14, or |a| <= 24 and |b| <= 12. G is the
+    same expression."""
+    _gemm_form(form)
+    fid = MFMA_FORMS.index(form)
     key = _mix32((int(seed) & _M32) ^ 0x47454D4D)
 
     def weights(size: int) -> List[int]:
@@ -418,8 +469,8 @@ def gemm_checksum(m: int, n: int, k: int, passes: int, seed: int) -> int:
     total = 0
     for kk in range(GEMM_K_PERIOD):
         cnt = int(k) // GEMM_K_PERIOD + (kk < int(k) % GEMM_K_PERIOD)
-        total += (cnt * sum(u[r] * _mfma_a(key, r, kk) for r in range(GEMM_ROW_PERIOD))
-                  * sum(v[r] * _mfma_b(key, kk, r) for r in range(GEMM_ROW_PERIOD)))
+        total += (cnt * sum(u[r] * _mfma_a(key, r, kk, fid) for r in range(GEMM_ROW_PERIOD))
+                  * sum(v[r] * _mfma_b(key, kk, r, fid) for r in range(GEMM_ROW_PERIOD)))
     return total * (int(passes) * (int(passes) + 1) // 2) % (1 << 64)
 
 
@@ -429,7 +480,7 @@ def _child_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="cotenancy", description=__doc__)
     p.add_argument("--child", action="store_true", required=True)
     p.add_argument("--device", type=int, default=0)
-    p.add_argument("--kind", choices=EVERY_KIND, default="fma")
+    p.add_argument("--kind", choices=TENANT_KINDS, default="fma")
     p.add_argument("--launches", type=int, default=8)
     p.add_argument("--iters", type=int, default=0)
     p.add_argument("--bytes", type=int, default=0)
@@ -557,7 +608,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
              operands: Optional[str] = None) -> Dict[str, Any]:
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
-    "fma" | "stream" | "cache" | "chase" | "mfma" | "gemm"} and may carry its own "launches", "iters",
+    "fma" | "stream" | "cache" | "chase" | "mfma" | "gemm" | "gemm-mxfp8" |
+    "gemm-mxfp4"} and may carry its own "launches", "iters",
     "bytes" and "passes" in place of the call-wide ones; `kinds`, when given,
     names the kinds instead. Every child warms up and says READY; only then
     are all told GO. Returns {"ok": True, "tenants": [the children's
@@ -574,8 +626,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     carry its own "operands" instead, an unknown value or "operands" on a
     tenant of another kind raises ValueError before anything is started,
     and a child is given --operands, after --form, only when one was named
-    for it. A gemm tenant is of another kind in this sense: it takes
-    neither.
+    for it. A gemm, gemm-mxfp8 or gemm-mxfp4 tenant is of another kind in
+    this sense: it takes neither.
 
     Each child has `timeout` seconds from its start. The first child that
     times out, exits non-zero or prints no TENANT line ends the run: the
@@ -601,7 +653,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     try:
         for i, tenant in enumerate(tenants):
             kind = kinds[i] if kinds is not None else tenant["kind"]
-            if kind not in EVERY_KIND:
+            if kind not in TENANT_KINDS:
                 raise ValueError(f"unknown tenant kind {kind!r}")
             env = dict(os.environ)
             env[ENV_CU_MASK] = mask_hex(int(tenant["mask"]))
@@ -672,7 +724,8 @@ def _balanced(launches: int, seconds: Sequence[float]) -> List[int]:
 
 # What a report knows of each kind. First the keys of a child's result that a
 # solo entry adds; a kind that adds clock_ghz gets the clock split in a pair.
-_SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",), "gemm": ("clock_ghz",)}
+_SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",), "gemm": ("clock_ghz",),
+              **{kind: ("clock_ghz",) for kind in MXGEMM_KINDS}}
 
 
 def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
@@ -689,6 +742,9 @@ def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
                              form or MFMA_FORMS[0], operands or MFMA_OPERANDS[0])
     if kind in GEMM_KINDS:
         return gemm_checksum(result["m"], result["n"], result["k"], result["passes"], seed)
+    if kind in MXGEMM_KINDS:
+        return gemm_checksum(result["m"], result["n"], result["k"], result["passes"], seed,
+                             form=kind[len("gemm-"):])
     return None
 
 
@@ -745,6 +801,13 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     cycle_ratio what the shared memory path took. It takes neither `form`
     nor `operands`; one on a gemm tenant raises ValueError.
 
+    A gemm-mxfp8 or gemm-mxfp4 tenant (pairs=mxgemm_pairs(kind)) is the
+    same with block-scaled operands: `iters` are steps of 128 or 256 k,
+    `bytes` the elements of A plus B, see gemm_shape(form=); its checksum is
+    held against gemm_checksum(form=), and its entries carry the clock and
+    its split as a gemm tenant's do. It too takes neither `form` nor
+    `operands`.
+
     `form` (one of MFMA_FORMS, anything else raises ValueError) is the
     instruction the mfma tenants issue, alone and in every pair; a tenant
     ({"mask": int, "form": str}) may name its own instead, for a bf16 tenant
@@ -773,11 +836,11 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     if len(tenants) != 2:
         raise ValueError("isolation_report takes two tenants")
     for pair in pairs:
-        if len(pair) != 2 or any(k not in EVERY_KIND for k in pair):
+        if len(pair) != 2 or any(k not in TENANT_KINDS for k in pair):
             raise ValueError(f"not a pair of tenant kinds: {pair!r}")
     windows = {kind: dict(w) for kind, w in (windows or {}).items()}
     for kind, w in windows.items():
-        if kind not in EVERY_KIND or any(k not in WINDOW_KEYS for k in w):
+        if kind not in TENANT_KINDS or any(k not in WINDOW_KEYS for k in w):
             raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
     # Per option and tenant, what the tenant is started with as an mfma one.
     named = {key: [_mfma_option(key, t, MATRIX_KINDS[0], wide) for t in tenants]
@@ -813,7 +876,7 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         return None
 
     for i, tenant in enumerate(tenants):
-        for kind in EVERY_KIND:
+        for kind in TENANT_KINDS:
             if not any(pair[i] == kind for pair in pairs):
                 continue
             run = run_pair(card, [{"mask": tenant["mask"], "kind": kind,

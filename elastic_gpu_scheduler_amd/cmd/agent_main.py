@@ -27,7 +27,8 @@ chip's and follows no mask; --co-tenancy-mfma-form runs that tenant with the
 FP8 or block-scaled MX instructions in place of the bf16 one, and
 --co-tenancy-mfma-operands lds with its operands re-read from LDS every step.
 --co-tenancy-gemm does it for the tenant all of those lead up to: a whole
-bf16 GEMM whose operands travel global memory -> LDS -> MFMA.
+bf16 GEMM whose operands travel global memory -> LDS -> MFMA;
+--co-tenancy-gemm-form runs that GEMM block-scaled, MXFP8 or MXFP4.
 """
 from __future__ import annotations
 
@@ -72,6 +73,17 @@ def mfma_forms_arg(text: str):
         raise argparse.ArgumentTypeError(
             f"expected forms out of {', '.join(MFMA_FORMS)} as FORM[,FORM...], "
             f"got {text!r}")
+    return forms
+
+
+def gemm_forms_arg(text: str):
+    """"FORM[,FORM...]": block-scaled forms of the gemm tenant."""
+    from elastic_gpu_scheduler_amd.agent.cotenancy import MXGEMM_KINDS
+
+    forms = tuple(text.split(","))
+    if not all("gemm-" + f in MXGEMM_KINDS for f in forms):
+        raise argparse.ArgumentTypeError(
+            f"expected forms out of mxfp8, mxfp4 as FORM[,FORM...], got {text!r}")
     return forms
 
 
@@ -160,6 +172,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "--co-tenancy-mfma; not together with "
                         "--co-tenancy-cache, --co-tenancy-chase or "
                         "--co-tenancy-mfma")
+    p.add_argument("--co-tenancy-gemm-form", type=gemm_forms_arg, default=None,
+                   metavar="FORM[,FORM...]",
+                   help="with --co-tenancy-gemm: run the GEMM tenant "
+                        "block-scaled, out of mxfp8 (e4m3 elements) and mxfp4 "
+                        "(e2m1), one E8M0 scale per row and block of 32 k: "
+                        "the kinds gemm-mxfp8 and gemm-mxfp4 in place of "
+                        "gemm in every pair; one report per card and form, "
+                        "one after another")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -196,7 +216,8 @@ def main(argv=None) -> int:
             ("--co-tenancy-mfma-form", "--co-tenancy-mfma", ()),
             ("--co-tenancy-mfma-operands", "--co-tenancy-mfma", ()),
             ("--co-tenancy-gemm", "--co-tenancy",
-             ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma"))):
+             ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma")),
+            ("--co-tenancy-gemm-form", "--co-tenancy-gemm", ())):
         if not given(flag):
             continue
         if not given(needs):
@@ -209,12 +230,15 @@ def main(argv=None) -> int:
 
     if args.co_tenancy is not None:
         from elastic_gpu_scheduler_amd.agent.cotenancy import (
-            CACHE_PAIRS, CHASE_PAIRS, GEMM_PAIRS, MFMA_PAIRS, cache_passes)
+            CACHE_PAIRS, CHASE_PAIRS, GEMM_PAIRS, MFMA_PAIRS, cache_passes, mxgemm_pairs)
 
         # What every report of the run is asked for and, where a flag names
         # several forms or sizes, what each of them adds, by its label.
         common, each = {}, None
-        if args.co_tenancy_gemm:
+        if args.co_tenancy_gemm_form is not None:
+            each = {form: {"pairs": mxgemm_pairs("gemm-" + form)}
+                    for form in args.co_tenancy_gemm_form}
+        elif args.co_tenancy_gemm:
             common = {"pairs": GEMM_PAIRS}
         elif args.co_tenancy_mfma:
             common = {"pairs": MFMA_PAIRS}

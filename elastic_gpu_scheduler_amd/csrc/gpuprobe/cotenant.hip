@@ -7,6 +7,8 @@
 //     along a chain of dependent loads, one in flight per wave ("chase"), or
 //     MFMAs (bf16, or the fp8, mxfp8 or mxfp4 form) issued back to back on
 //     operands held in registers or re-read from LDS every step ("mfma"),
+//     or a whole GEMM fed from memory through LDS, bf16 ("gemm") or
+//     block-scaled ("gemm-mxfp8", "gemm-mxfp4"),
 //     each launch stamped with the device's constant-rate wall clock. The
 //     clock is the card's, not the
 //     process's, so two separate processes can lay their launches side by
@@ -26,6 +28,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -1032,13 +1035,460 @@ tenant_gemm_kernel(const int4v* __restrict__ a, const int4v* __restrict__ b, uin
   clocked_end(rec, clk, c0, t0);
 }
 
+// ---- gemm-mxfp8, gemm-mxfp4 ------------------------------------------------
+
+using int2v = __attribute__((ext_vector_type(2))) int;
+
+// What tenant_gemm_kernel leaves, as functions. Part one: the lane's 64
+// accumulators as integers,
+// the entry at (m, n), global, weighed by (1 + m) (1 + n) modulo 2^64. The
+// wave's tile starts at (row0 + 64 (wave >> 1), col0 + 64 (wave & 1)).
+__device__ inline uint64_t gemm_tile_sum(const MfmaTile& acc, uint32_t row0, uint32_t col0,
+                                         uint32_t wave, uint32_t r, uint32_t h) {
+  uint64_t sum = 0;
+#pragma unroll
+  for (uint32_t t = 0; t < 4; ++t) {
+    const uint32_t m = row0 + 64 * (wave >> 1) + 32 * (t >> 1) + 4 * h;
+    const uint32_t n = col0 + 64 * (wave & 1u) + 32 * (t & 1u) + r;
+    uint64_t column = 0;
+#pragma unroll
+    for (uint32_t reg = 0; reg < 16; ++reg)
+      column += static_cast<uint64_t>(static_cast<int64_t>(
+                    static_cast<int>(acc[t >> 1][t & 1][reg]))) *
+                static_cast<uint64_t>(1 + m + (reg & 3u) + 8 * (reg >> 2));
+    sum += column * static_cast<uint64_t>(1 + n);
+  }
+  return sum;
+}
+
+// Part two: the 256 sums added up through LDS, the workgroup's one word
+// stored by thread 0.
+__device__ inline void gemm_store_sum(unsigned long long* sums, uint64_t sum,
+                                      unsigned long long* __restrict__ out) {
+  sums[threadIdx.x] = sum;
+  __syncthreads();
+  for (uint32_t width = kBlock / 2; width > 0; width >>= 1) {
+    if (threadIdx.x < width) sums[threadIdx.x] += sums[threadIdx.x + width];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = sums[0];
+}
+
+// What the two block-scaled GEMMs differ in. A slab row is 128 bytes in
+// either form, as in the bf16 kernel: 128 k of e4m3 or 256 k of e2m1, that is
+// two or four sub-steps of 64 k (one MFMA deep) and four or eight blocks of
+// 32 k, each with its own E8M0 scale byte. A row's scale bytes of one step
+// are one word of 4 or 8 bytes, block b in byte b. K stays exact up to
+// kMaxIters steps (see the kernel). agent/cotenancy.py keeps the same table.
+template <int F>
+struct MxGemm {
+  static_assert(F == kMxfp8 || F == kMxfp4, "a block-scaled form");
+  static constexpr int kSub = F == kMxfp8 ? 2 : 4;
+  static constexpr int kStepK = 64 * kSub;
+  static constexpr int kWordBytes = 2 * kSub;
+  static constexpr int kWordDwords = kWordBytes / 4;
+  static constexpr int kMaxIters = F == kMxfp8 ? 256 : 64;  // K <= 32768, 16384
+  static constexpr int kDefaultIters = 4096 / kStepK;
+  // 16-byte LDS reads per sub-step, and how many of them go in front of one
+  // MFMA: two per 32 cycles of MFMA, and the mxfp8 MFMA takes 64.
+  static constexpr int kReads = F == kMxfp8 ? 8 : 4;
+  static constexpr int kReadsPerGap = F == kMxfp8 ? 4 : 2;
+  using Word = typename std::conditional<F == kMxfp8, int, int2v>::type;
+  __device__ static uint32_t dword(Word w, int d) {
+    if constexpr (F == kMxfp8) return static_cast<uint32_t>(w);
+    else return static_cast<uint32_t>(w[d]);
+  }
+};
+constexpr int kMxGemmDefaultSide = 8192;
+constexpr int kMxGemmDefaultPasses[kMfmaForms] = {0, 0, 32, 64};
+
+// The operands of a block-scaled gemm tenant. `buf` is A (S x K, row-major)
+// followed by B (S x K, row n holding column n), e4m3 bytes or e2m1 nibbles,
+// low nibble first: element (row, k) is that of MfmaFrags<F> at mfma_a_hash<F>
+// (key, row % 192, k % 96) or mfma_b_hash<F>(key, k % 96, row % 192), mxfp8
+// hash % 15 - 7 and mxfp4 the code hash & 15. One 16-byte store of 16 or 32
+// elements per step, grid-stride; v16 = 8 x steps counts the stores of a row
+// and n16 = 2 S v16 those of both matrices. 96 is a multiple of 16 and of 32,
+// so a store never straddles the k period.
+//
+// `scales` is step-major: A's words [steps][S], then B's [steps][S], one word
+// per row and step, byte b the scale of the step's block b, that is of block
+// ((k % 96) / 32) of the hashes with k = kStepK x step + 32 b: mxfp8 127 + e
+// on both sides, mxfp4 128 + e for A and 128 for B, e the form's scale bit.
+// So the 32 rows of a fragment are 128 or 256 contiguous bytes. nwords = 2 x
+// steps x S. All indices are 64-bit, below n16 and below nwords.
+template <int F>
+__global__ void __launch_bounds__(kBlock)
+tenant_mxgemm_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint64_t v16,
+                          typename MxGemm<F>::Word* __restrict__ scales, uint64_t nwords,
+                          uint64_t s, uint32_t key) {
+  using G = MxGemm<F>;
+  constexpr uint32_t kPerDword = F == kMxfp8 ? 4 : 8;  // elements of one dword
+  const uint64_t first = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+  for (uint64_t i = first; i < n16; i += stride) {
+    const bool is_b = i >= n16 / 2;
+    const uint64_t at = is_b ? i - n16 / 2 : i;
+    const uint32_t row = static_cast<uint32_t>((at / v16) % kGemmRowPeriod);
+    const uint32_t k0 = static_cast<uint32_t>((at % v16) * (4 * kPerDword) % kGemmKPeriod);
+    int4v v;
+#pragma unroll
+    for (uint32_t d = 0; d < 4; ++d) {
+      uint32_t word = 0;
+#pragma unroll
+      for (uint32_t q = 0; q < kPerDword; ++q) {
+        const uint32_t k = k0 + kPerDword * d + q;
+        const uint32_t hash = is_b ? mfma_b_hash<F>(key, k, row) : mfma_a_hash<F>(key, row, k);
+        if constexpr (F == kMxfp8)
+          word |= to_e4m3_bits(static_cast<int>(hash % 15u) - 7) << (8 * q);
+        else
+          word |= (hash & 15u) << (4 * q);
+      }
+      v[d] = static_cast<int>(word);
+    }
+    buf[i] = v;
+  }
+  for (uint64_t i = first; i < nwords; i += stride) {
+    const bool is_b = i >= nwords / 2;
+    const uint64_t at = is_b ? i - nwords / 2 : i;
+    const uint32_t row = static_cast<uint32_t>((at % s) % kGemmRowPeriod);
+    const uint32_t blk0 = static_cast<uint32_t>((at / s) * G::kWordBytes % 3);
+    uint32_t word[2] = {0, 0};
+#pragma unroll
+    for (uint32_t b = 0; b < G::kWordBytes; ++b) {
+      const uint32_t blk = (blk0 + b) % 3;
+      uint32_t byte;
+      if constexpr (F == kMxfp8)
+        byte = 127u + (is_b ? mfma_b_scale_bit<F>(key, blk, row)
+                            : mfma_a_scale_bit<F>(key, row, blk));
+      else
+        byte = 128u + (is_b ? 0u : mfma_a_scale_bit<F>(key, row, blk));
+      word[b / 4] |= byte << (8 * (b % 4));
+    }
+    if constexpr (F == kMxfp8)
+      scales[i] = static_cast<int>(word[0]);
+    else
+      scales[i] = int2v{static_cast<int>(word[0]), static_cast<int>(word[1])};
+  }
+}
+
+// Buffer loads (raw, no stride): the descriptor's last word for gfx9 (32-bit
+// data format), and an offset no descriptor here reaches: every window is
+// below 2^31 bytes (a matrix is at most 32768 x 32768 bytes, the scale words
+// of one operand 32 MiB), whether or not the hardware counts the shared
+// offset into its range check.
+constexpr int kBufferWord3 = 0x00020000;
+constexpr uint32_t kBufferOutside = 0x80000000u;
+
+template <int F>
+__device__ inline typename MxGemm<F>::Word mx_load_word(__amdgpu_buffer_rsrc_t window,
+                                                        uint32_t lane_off, uint32_t shared_off) {
+  if constexpr (F == kMxfp8)
+    return static_cast<int>(__builtin_amdgcn_raw_buffer_load_b32(window, lane_off, shared_off, 0));
+  else
+    return __builtin_bit_cast(
+        int2v, __builtin_amdgcn_raw_buffer_load_b64(window, lane_off, shared_off, 0));
+}
+
+// One step's loads of a lane, as they come from global memory: its eight
+// chunks of the two slabs and the scale words of its four fragments' rows.
+template <int F>
+struct MxPrefetch {
+  int4v slab[2][kGemmLoads];
+  typename MxGemm<F>::Word sa[2], sb[2];
+};
+
+// The scale words of the step being multiplied, shifted right by 8 h: byte 0
+// of dword d is the scale of block 4 d + h and byte 2 that of block 4 d + 2 +
+// h, the two blocks lane r + 32 h supplies the scale of (see MfmaFrags).
+template <int F>
+struct MxScales {
+  int a[2][MxGemm<F>::kWordDwords], b[2][MxGemm<F>::kWordDwords];
+  __device__ void take(const MxPrefetch<F>& p, uint32_t h) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int d = 0; d < MxGemm<F>::kWordDwords; ++d) {
+        a[t][d] = static_cast<int>(MxGemm<F>::dword(p.sa[t], d) >> (8 * h));
+        b[t][d] = static_cast<int>(MxGemm<F>::dword(p.sb[t], d) >> (8 * h));
+      }
+  }
+};
+
+// Sub-step S of a step: acc[m][n] += A_m x B_n over 64 k, the fragments under
+// the scales of blocks 2 S + h. The lane's byte is byte 2 (S & 1) of dword S
+// >> 1 of the shifted word, picked by the scale operands' op_sel: no VALU
+// work per sub-step, and every checksum on the card came out exact with it
+// (profiles/mxgemm_cotenancy_results.md). With GPUPROBE_MXGEMM_SHIFT_SCALES
+// defined the byte is shifted down to byte 0 instead and op_sel stays 0; that
+// build was not run.
+template <int F, int S>
+__device__ inline void mx_step(const MfmaFrags<F>& f, MfmaTile& acc, const MxScales<F>& sc) {
+#ifdef GPUPROBE_MXGEMM_SHIFT_SCALES
+  constexpr int kSel = 0, kShift = 16 * (S & 1);
+#else
+  constexpr int kSel = 2 * (S & 1), kShift = 0;
+#endif
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int m = t >> 1, n = t & 1;
+    const int sa = static_cast<int>(static_cast<uint32_t>(sc.a[m][S >> 1]) >> kShift);
+    const int sb = static_cast<int>(static_cast<uint32_t>(sc.b[n][S >> 1]) >> kShift);
+    if constexpr (F == kMxfp8)
+      acc[m][n] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(f.a[m], f.b[n], acc[m][n], 0,
+                                                                  0, kSel, sa, kSel, sb);
+    else
+      acc[m][n] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+          MfmaFrags<F>::widen(f.a[m]), MfmaFrags<F>::widen(f.b[n]), acc[m][n], 4, 4, kSel, sa,
+          kSel, sb);
+  }
+}
+
+// A block-scaled GEMM, MXFP8 (e4m3) or MXFP4 (e2m1) elements under E8M0
+// scales per block of 32 k, whose elements travel global memory -> LDS ->
+// MFMA and whose scales travel global memory -> registers: C (S x S, f32
+// accumulators, never stored) = A (S x K) . B^T, B stored S x K, K = 128
+// (mxfp8) or 256 (mxfp4) x steps, S = 128 x side. Grid, tile walk
+// (gemm_order), work split, slab geometry and result are tenant_gemm_kernel's;
+// the pipeline and the scale path are this kernel's own.
+//
+// Work split. A workgroup owns a 128 x 128 tile of C, its four waves 2 x 2 on
+// 64 x 64 each as an MfmaTile. A step is a slab row of 128 bytes, two (mxfp8)
+// or four (mxfp4) sub-steps of four v_mfma_scale_f32_32x32x64_f8f6f4: per
+// wave and step 8 MFMAs of 64 cycles or 16 of 32, 512 cycles as for bf16.
+// The fragment rule is MfmaFrags<F>'s: lane r + 32 h of fragment t holds row
+// or column 32 t + r; for mxfp4 its four dwords are block 2 s + h of sub-step
+// s, one 16-byte chunk, 2 s + h, the bf16 kernel's addressing; for mxfp8 its
+// low four dwords are half h of block 2 s, chunk 4 s + h, and its high four
+// half h of block 2 s + 1, chunk 4 s + 2 + h, two reads per fragment.
+//
+// Data movement and LDS layout are the bf16 kernel's: lane t loads chunk t & 7
+// of rows (t >> 3) + 32 i of either slab, eight 16-byte loads a step; two
+// buffers of {A slab, B slab}, 64 KiB, and 2 KiB for the reduction; chunk c of
+// row R at chunk position c ^ q(R), q(R) = (R & 6) | ((R >> 3) & 1)
+// (gemm_slot). Its proof holds for these chunk indices: every fragment read
+// is a ds_read_b128 with lane r on row base + r (base a multiple of 32) at one
+// chunk per h, and the chunks of h = 0 and h = 1 are c and c ^ 1 here too (2
+// s, 4 s and 4 s + 2 are even); over 16 consecutive r, (r & 1, q(r)) takes all
+// 16 values, so 16 lanes of one h fall into 16 different groups of four
+// banks, and eight lanes of each h, should the hardware pair them so, meet
+// the keys q(0..7) = {0, 2, 4, 6} with c and c ^ 1 and stay apart as well.
+// The slab writes are the bf16 kernel's own. No bank conflict either way.
+//
+// Pipeline: two slabs in flight. A dependent load from HBM takes 375-399 ns
+// on an idle card (profiles/chase_cotenancy_results.md), about 900 cycles,
+// and a step is 512 cycles of MFMA, so a prefetch distance of one step, the
+// bf16 kernel's, cannot cover it. Here the global loads of step i + 2 are
+// issued at the top of step i into register set i & 1 (the set's loads of
+// step i were written to LDS a step before) and written to LDS buffer i & 1
+// at the end of step i + 1; every wave left that buffer through the barrier
+// that ended step i. Still two LDS buffers and one barrier per step. The
+// prologue loads steps 0 and 1 and writes step 0; the loop runs two steps an
+// iteration so that each register set is a fixed one; an odd last step
+// follows the loop. The last two steps load nothing: their loads are issued
+// all the same, but with every lane's offset outside the buffer descriptors'
+// range, which the hardware answers with zeros without reading memory, and
+// what they return is written to an LDS buffer nobody reads again (steps = 1
+// and 2 included). So no load has a branch around it, and every wait in
+// front of a slab write leaves exactly the newer step's twelve loads
+// outstanding (vmcnt counts in order).
+//
+// Scales. The scale words of a step go global -> registers at the same
+// distance and never touch LDS: every lane loads the word of each of its own
+// four rows, A at t = 0, 1 and B at t = 0, 1, lanes r and r + 32 the same
+// one, first in the step's loads so that they are there when its slabs are.
+// The words are step-major (see the fill), so a fragment's 32 lanes read 128
+// or 256 contiguous bytes. Once per step the words are shifted right by 8 h
+// (MxScales); a sub-step picks its byte with op_sel (mx_step).
+//
+// Within a step the fragment reads of sub-step s + 1 go in front of the MFMAs
+// of sub-step s into a second register set (mfma_lds_interleave), at most two
+// 16-byte reads per 32 cycles of MFMA: 4 + 4 in front of the first two mxfp8
+// MFMAs, 2 + 2 for mxfp4.
+//
+// Bounds. S and K are multiples of the tile and of the step, so nothing is
+// masked. A global element index is (128 tile + row) * 8 steps + 8 step +
+// chunk with tile < side, row < 128, step < steps and chunk < 8, below S * 8
+// steps, the 16-byte elements of one matrix; every descriptor ends where its
+// matrix or scale array does, and a load past the last step is outside it by
+// construction (offset bit 31). A scale index is step * S + row with step < steps and
+// row < S, below steps * S, one operand's words. An LDS index is gemm_slot of
+// a row below 128 and a chunk below 8 (4 s + 2 + h <= 7, 2 s + h <= 7), below
+// the slab's 1024.
+//
+// Exactness. Effective elements are integers. mxfp8: |a b| <= 14 * 14 and 196
+// * 32768 < 2^23, so K <= 32768, 256 steps. mxfp4: |A| <= 24 and |B| <= 12,
+// 288 * 16384 < 2^23 but 288 * 32768 > 2^23, so K <= 16384, 64 steps. Every
+// accumulator is an exact integer in f32 at every step.
+//
+// Result, stamps and clocks are the bf16 kernel's (gemm_tile_sum,
+// gemm_store_sum, clocked_end). No FP32 arithmetic but the MFMAs' is written
+// here or in the fill.
+//
+// hipcc -O3 for gfx950 reports (-Rpass-analysis=kernel-resource-usage), mxfp8
+// and mxfp4: 227 and 207 VGPRs (64 of accumulators, 64 and 32 of fragments,
+// 64 of prefetched slabs, 12 and 24 of scale words), no AGPRs, 54 SGPRs, no
+// scratch and no spills, 67584 bytes of LDS and an occupancy of 2 waves per
+// SIMD: two workgroups per CU still fit, by registers (256 a wave) and by
+// LDS alike. To get there no lane carries a 64-bit address (buffer loads)
+// and the loop has one exit: with a second exit in its middle the compiler
+// kept the accumulators twice and spilled.
+//
+// On the card (profiles/mxgemm_cotenancy_results.md) a SIMD spends 147-150
+// cycles per mxfp8 MFMA and 84-87 per mxfp4 one, where the instructions take
+// 64 and 32: per step and wave about 1190 and 1360 cycles against the bf16
+// kernel's 1120. The second slab in flight did not bring the step nearer its
+// 512 cycles of MFMA.
+template <int F>
+__global__ void __launch_bounds__(kBlock, 2)
+tenant_mxgemm_kernel(const int4v* __restrict__ a, const int4v* __restrict__ b,
+                     const typename MxGemm<F>::Word* __restrict__ sa,
+                     const typename MxGemm<F>::Word* __restrict__ sb, uint32_t side,
+                     uint32_t steps, unsigned long long* __restrict__ out,
+                     unsigned long long* __restrict__ rec,
+                     unsigned long long* __restrict__ clk) {
+  using G = MxGemm<F>;
+  using Slabs = int4v (*)[kGemmSlabVecs];
+  __shared__ int4v slab[2][2][kGemmSlabVecs];  // [buffer][A, B]
+  __shared__ unsigned long long sums[kBlock];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = lane & 31u, h = lane >> 5;
+  const uint32_t wave = threadIdx.x / 64;
+  const uint32_t tiles = side * side;
+  const uint32_t tile = gemm_order(blockIdx.x % tiles, tiles, side);
+  const uint32_t row0 = (tile >> 16) * kGemmTile, col0 = (tile & 0xFFFFu) * kGemmTile;
+  // What this lane loads: chunk threadIdx & 7 of rows (threadIdx >> 3) + 32 i,
+  // and the scale words of rows 64 x (wave's half) + 32 t + r, all as buffer
+  // loads: a descriptor the workgroup shares (from the tile's first row to
+  // the matrix's end, below 2^31 bytes), one 32-bit byte offset of the lane's
+  // and one the workgroup shares, so that the addresses of a step's twelve
+  // loads cost three vector registers and no load has a branch around it.
+  const uint32_t row_bytes = steps * (kGemmRowVecs * 16);
+  const uint32_t s_rows = side * kGemmTile;
+  const uint32_t load_row = threadIdx.x >> 3, load_c = threadIdx.x & 7u;
+  const uint32_t load_at = load_row * row_bytes + load_c * 16;
+  const uint32_t write_at = gemm_slot(load_row, load_c);  // + 32 rows: + 256
+  const uint32_t scale_a_at = (64 * (wave >> 1) + r) * G::kWordBytes;
+  const uint32_t scale_b_at = (64 * (wave & 1u) + r) * G::kWordBytes;
+  const auto window = [](const auto* first, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(first)),
+                                             0, static_cast<int>(bytes), kBufferWord3);
+  };
+  const auto ra = window(a + static_cast<uint64_t>(row0) * (row_bytes / 16),
+                         (s_rows - row0) * row_bytes);
+  const auto rb = window(b + static_cast<uint64_t>(col0) * (row_bytes / 16),
+                         (s_rows - col0) * row_bytes);
+  const auto rsa = window(sa + row0, (steps * s_rows - row0) * G::kWordBytes);
+  const auto rsb = window(sb + col0, (steps * s_rows - col0) * G::kWordBytes);
+  // What this lane reads: rows 64 x (wave's half) + 32 t + r of either slab;
+  // 32 t and 64 leave the row's key alone.
+  const uint32_t read_a = (64 * (wave >> 1) + r) * kGemmRowVecs;
+  const uint32_t read_b = (64 * (wave & 1u) + r) * kGemmRowVecs;
+  const uint32_t read_key = gemm_key(r);
+
+  MxPrefetch<F> p0, p1;
+  MxScales<F> cur;
+  // The loads of step `at_step`; past the last step every lane's offset is
+  // moved out of the descriptors' range, where a buffer load returns zeros
+  // and reads no memory.
+  const auto fetch = [&](MxPrefetch<F>& p, uint32_t at_step) __attribute__((always_inline)) {
+    const uint32_t outside = at_step < steps ? 0u : kBufferOutside;
+    const uint32_t word_off = at_step * s_rows * G::kWordBytes;
+    const uint32_t slab_off = at_step * (kGemmRowVecs * 16);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      p.sa[t] = mx_load_word<F>(rsa, (scale_a_at | outside) + 32 * t * G::kWordBytes, word_off);
+      p.sb[t] = mx_load_word<F>(rsb, (scale_b_at | outside) + 32 * t * G::kWordBytes, word_off);
+    }
+#pragma unroll
+    for (int i = 0; i < kGemmLoads; ++i) {
+      p.slab[0][i] = __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(
+          ra, load_at | outside, slab_off + 32 * i * row_bytes, 0));
+      p.slab[1][i] = __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(
+          rb, load_at | outside, slab_off + 32 * i * row_bytes, 0));
+    }
+  };
+  const auto store = [&](const MxPrefetch<F>& p, Slabs to) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < kGemmLoads; ++i) {
+      to[0][write_at + 32 * kGemmRowVecs * i] = p.slab[0][i];
+      to[1][write_at + 32 * kGemmRowVecs * i] = p.slab[1][i];
+    }
+  };
+  const auto read = [&](MfmaFrags<F>& f, Slabs from, uint32_t s) __attribute__((always_inline)) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int4v* ra = from[0] + read_a + 32 * kGemmRowVecs * t;
+      const int4v* rb = from[1] + read_b + 32 * kGemmRowVecs * t;
+      if constexpr (F == kMxfp8) {
+        const uint32_t lo = (4 * s + h) ^ read_key, hi = (4 * s + 2 + h) ^ read_key;
+        const int4v al = ra[lo], ah = ra[hi], bl = rb[lo], bh = rb[hi];
+        f.a[t] = int8v{al[0], al[1], al[2], al[3], ah[0], ah[1], ah[2], ah[3]};
+        f.b[t] = int8v{bl[0], bl[1], bl[2], bl[3], bh[0], bh[1], bh[2], bh[3]};
+      } else {
+        const uint32_t c = (2 * s + h) ^ read_key;
+        f.a[t] = ra[c];
+        f.b[t] = rb[c];
+      }
+    }
+  };
+  f32x16 acc[2][2];
+  // One step's MFMAs on the slabs of `from` under the scales of `cur`.
+  const auto multiply = [&](Slabs from) __attribute__((always_inline)) {
+    MfmaFrags<F> f[2];
+    read(f[0], from, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    read(f[1], from, 1);
+    mx_step<F, 0>(f[0], acc, cur);
+    mfma_lds_interleave<G::kReads, G::kReadsPerGap>();
+    if constexpr (G::kSub == 4) {
+      read(f[0], from, 2);
+      mx_step<F, 1>(f[1], acc, cur);
+      mfma_lds_interleave<G::kReads, G::kReadsPerGap>();
+      read(f[1], from, 3);
+      mx_step<F, 2>(f[0], acc, cur);
+      mfma_lds_interleave<G::kReads, G::kReadsPerGap>();
+      mx_step<F, 3>(f[1], acc, cur);
+    } else {
+      mx_step<F, 1>(f[1], acc, cur);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  // Step i on buffer i & 1 with the scales of `mine`, whose loads those of
+  // step i + 2 replace; `next`, step i + 1, goes to the other buffer behind
+  // the MFMAs.
+  const auto step = [&](MxPrefetch<F>& mine, uint32_t i, const MxPrefetch<F>& next)
+      __attribute__((always_inline)) {
+    cur.take(mine, h);
+    fetch(mine, i + 2);
+    multiply(slab[i & 1u]);
+    store(next, slab[(i + 1) & 1u]);
+    __syncthreads();
+  };
+
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  const unsigned long long t0 = stamp_start();
+  mfma_zero(acc);
+  fetch(p0, 0);
+  fetch(p1, 1);
+  store(p0, slab[0]);
+  __syncthreads();
+  for (uint32_t i = 0; i + 1 < steps; i += 2) {
+    step(p0, i, p1);
+    step(p1, i + 1, p0);
+  }
+  if (steps & 1u) step(p0, steps - 1, p1);
+  gemm_store_sum(sums, gemm_tile_sum(acc, row0, col0, wave, r, h), out);
+  clocked_end(rec, clk, c0, t0);
+}
+
 // ---- host ------------------------------------------------------------------
 
-enum class Kind : int { kFma, kStream, kCache, kChase, kMfma, kGemm };
-constexpr int kKinds = 6;
+enum class Kind : int { kFma, kStream, kCache, kChase, kMfma, kGemm, kGemmMxfp8, kGemmMxfp4 };
+constexpr int kKinds = 8;
 // Per kind: name, workgroups per CU (chase: one, that is one wave per SIMD;
-// gemm: none, its grid is the problem's), whether it reads a buffer filled
-// beforehand, whether it takes form and operands.
+// the gemms: none, their grid is the problem's), whether it reads a buffer
+// filled beforehand, whether it takes form and operands.
 struct KindInfo {
   const char* name;
   int groups_per_cu;
@@ -1047,7 +1497,13 @@ struct KindInfo {
 constexpr KindInfo kKindTable[kKinds] = {
     {"fma", kGroupsPerCu, false, false},   {"stream", kGroupsPerCu, true, false},
     {"cache", kCacheGroupsPerCu, true, false}, {"chase", 1, true, false},
-    {"mfma", kMfmaGroupsPerCu, false, true},   {"gemm", 0, true, false}};
+    {"mfma", kMfmaGroupsPerCu, false, true},   {"gemm", 0, true, false},
+    {"gemm-mxfp8", 0, true, false},            {"gemm-mxfp4", 0, true, false}};
+
+// Whether a kind is one of the three GEMMs, and whether a block-scaled one;
+// the form of the latter is the kind's.
+constexpr bool is_gemm(Kind k) { return k >= Kind::kGemm; }
+constexpr bool is_mxgemm(Kind k) { return k > Kind::kGemm; }
 
 // The kernel of an mfma tenant: [operands from LDS][form].
 using MfmaKernel = decltype(&tenant_mfma_kernel<kBf16>);
@@ -1087,7 +1543,7 @@ struct TenantResult {
   bool skipped = false;
   uint64_t free_bytes = 0;
   Kind kind = Kind::kFma;
-  int form = kBf16;  // mfma only
+  int form = kBf16;  // mfma, and the block-scaled gemms, whose kind names it
   bool lds = false;  // mfma only: operands re-read from LDS
   uint64_t lds_bytes = 0, lds_bytes_per_launch = 0;  // mfma from LDS only
   MaskWords applied;
@@ -1098,6 +1554,7 @@ struct TenantResult {
   uint64_t nodes = 0, stride = 0;  // chase only
   int side = 0, tiles = 0;         // gemm only: tiles per side and per pass
   uint64_t m = 0, n = 0, k = 0;    // gemm only
+  uint64_t scale_bytes = 0;        // block-scaled gemm only: A's and B's scale words
   uint64_t load_bytes_per_launch = 0;  // gemm only
   // flops (fma, mfma, gemm), bytes (stream, cache) or hops (chase)
   double work_per_launch = 0.0;
@@ -1183,6 +1640,34 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
           static_cast<uint64_t>(r.workgroups) * 2 * kGemmTile * r.k * 2;
       break;
     }
+    case Kind::kGemmMxfp8:
+    case Kind::kGemmMxfp4: {
+      // agent/cotenancy.py states the same rule on its own (gemm_shape). A
+      // row of A plus one of B is 256 bytes a step in either form.
+      const bool f8 = kind == Kind::kGemmMxfp8;
+      r.form = f8 ? kMxfp8 : kMxfp4;
+      const int step_k = f8 ? MxGemm<kMxfp8>::kStepK : MxGemm<kMxfp4>::kStepK;
+      const uint64_t word = f8 ? MxGemm<kMxfp8>::kWordBytes : MxGemm<kMxfp4>::kWordBytes;
+      if (iters <= 0) iters = 4096 / step_k;
+      r.iters = std::min(iters, f8 ? MxGemm<kMxfp8>::kMaxIters : MxGemm<kMxfp4>::kMaxIters);
+      r.k = static_cast<uint64_t>(step_k) * r.iters;
+      const uint64_t s = bytes == 0 ? kMxGemmDefaultSide
+                                    : bytes / (256ULL * r.iters) / kGemmTile * kGemmTile;
+      r.m = r.n = std::min<uint64_t>(std::max<uint64_t>(s, kGemmTile), kGemmMaxSide);
+      r.bytes = 256 * r.m * r.iters;
+      r.scale_bytes = 2 * r.m * r.iters * word;
+      r.side = static_cast<int>(r.m / kGemmTile);
+      r.tiles = r.side * r.side;
+      if (passes <= 0) passes = kMxGemmDefaultPasses[r.form];
+      r.passes = std::min(passes, kGemmMaxGroups / r.tiles);
+      r.workgroups = r.tiles * r.passes;
+      r.work_per_launch = 2.0 * r.m * r.n * r.k * r.passes;
+      // Per workgroup and step two slabs of 16 KiB, and per wave the words of
+      // its 64 rows of A and 64 of B (lanes r and r + 32 ask for the same one).
+      r.load_bytes_per_launch = static_cast<uint64_t>(r.workgroups) * r.iters *
+                                (2 * kGemmSlabVecs * 16 + kWavesPerGroup * kGemmTile * word);
+      break;
+    }
   }
   return r;
 }
@@ -1194,20 +1679,23 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
   const dim3 grid(r.workgroups);
   // What a launch leaves: a word per lane, for gemm one per workgroup.
   const size_t lanes =
-      static_cast<size_t>(r.workgroups) * (r.kind == Kind::kGemm ? 1 : kBlock);
+      static_cast<size_t>(r.workgroups) * (is_gemm(r.kind) ? 1 : kBlock);
   const uint64_t n16 = r.bytes / 16;
-  DevBuf buf, out;
+  DevBuf buf, scales, out;
   Mirror recs{r.recs}, clks{r.clks};
   // One record {~0, 0} per timed launch, and one more for the warm-up.
   recs.h.assign(2 * static_cast<size_t>(launches + 1), 0ULL);
   for (size_t i = 0; i < recs.h.size(); i += 2) recs.h[i] = ~0ULL;
   if (kKindTable[static_cast<int>(r.kind)].reads) buf.alloc(r.bytes);
+  if (is_mxgemm(r.kind)) scales.alloc(r.scale_bytes);
   switch (r.kind) {  // what a lane stores, and what else a launch records
     case Kind::kFma:
       out.alloc(lanes * sizeof(float));
       break;
     case Kind::kMfma:  // {sum of shader cycles, sum of wall ticks}, from zero
     case Kind::kGemm:
+    case Kind::kGemmMxfp8:
+    case Kind::kGemmMxfp4:
       clks.h.assign(recs.h.size(), 0ULL);
       [[fallthrough]];
     default:
@@ -1227,6 +1715,13 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
       HIP_CHECK(hipGetLastError());
     };
     unsigned long long* const o64 = out.as<unsigned long long>();
+    // A, then B behind it; A's scale words, then B's behind them.
+    const auto mxgemm = [&](auto kernel, auto* words, unsigned long long* rec,
+                            unsigned long long* clk) {
+      go(grid, kernel, buf.as<const int4v>(), buf.as<const int4v>() + n16 / 2, words,
+         words + r.m * r.iters, static_cast<uint32_t>(r.side), static_cast<uint32_t>(r.iters),
+         o64, rec, clk);
+    };
     const auto launch = [&](int slot) {
       unsigned long long* rec = recs.at(2 * slot);
       switch (r.kind) {
@@ -1251,7 +1746,20 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
              static_cast<uint32_t>(r.side), static_cast<uint32_t>(r.iters), o64, rec,
              clks.at(2 * slot));
           break;
+        case Kind::kGemmMxfp8:
+          mxgemm(tenant_mxgemm_kernel<kMxfp8>, scales.as<const int>(), rec, clks.at(2 * slot));
+          break;
+        case Kind::kGemmMxfp4:
+          mxgemm(tenant_mxgemm_kernel<kMxfp4>, scales.as<const int2v>(), rec,
+                 clks.at(2 * slot));
+          break;
       }
+    };
+    // The fill of a block-scaled gemm: elements, then A's and B's scale words.
+    const auto mxfill = [&](auto kernel, auto* words) {
+      go(dim3(kGroupsPerCu * cus), kernel, buf.as<int4v>(), n16,
+         static_cast<uint64_t>(r.iters) * kGemmRowVecs, words, 2 * r.m * r.iters, r.m,
+         mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
     };
     switch (r.kind) {  // the fill
       case Kind::kStream:
@@ -1265,6 +1773,12 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
       case Kind::kGemm:
         go(dim3(kGroupsPerCu * cus), tenant_gemm_fill_kernel, buf.as<int4v>(), n16, r.k / 8,
            mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
+        break;
+      case Kind::kGemmMxfp8:
+        mxfill(tenant_mxgemm_fill_kernel<kMxfp8>, scales.as<int>());
+        break;
+      case Kind::kGemmMxfp4:
+        mxfill(tenant_mxgemm_fill_kernel<kMxfp4>, scales.as<int2v>());
         break;
       default:
         break;
@@ -1323,8 +1837,10 @@ void summarise(TenantResult& r) {
       break;
     case Kind::kMfma:  // every lane's fold weighted likewise
     case Kind::kGemm:  // every workgroup's word weighted by its pass, from 1
+    case Kind::kGemmMxfp8:
+    case Kind::kGemmMxfp4:
       for (size_t g = 0; g < r.out.size(); ++g)
-        r.checksum += (r.kind == Kind::kGemm ? 1 + g / r.tiles : g + 1) * r.out[g];
+        r.checksum += (is_gemm(r.kind) ? 1 + g / r.tiles : g + 1) * r.out[g];
       for (size_t l = 0; l < r.launches.size(); ++l) {
         Launch& e = r.launches[l];
         e.cycles = r.clks[2 * l];
@@ -1354,7 +1870,7 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     r.free_bytes = free_b;
-    if (free_b < r.bytes + kGiB) {
+    if (free_b < r.bytes + r.scale_bytes + kGiB) {
       r.skipped = true;
       return r;
     }
@@ -1383,7 +1899,7 @@ void register_cotenant(py::module_& m) {
         if (k == kKinds)
           throw py::value_error(
               "cu_tenant_run: kind must be \"fma\", \"stream\", \"cache\", "
-              "\"chase\", \"mfma\" or \"gemm\"");
+              "\"chase\", \"mfma\", \"gemm\", \"gemm-mxfp8\" or \"gemm-mxfp4\"");
         int f = 0;
         while (f < kMfmaForms && form != kMfmaFormTable[f].name) ++f;
         if (f == kMfmaForms)
@@ -1454,10 +1970,14 @@ void register_cotenant(py::module_& m) {
             last["clock_ghz"] = r.clock_ghz;
             break;
           case Kind::kGemm:
+          case Kind::kGemmMxfp8:
+          case Kind::kGemmMxfp4:
+            if (is_mxgemm(r.kind)) d["form"] = kMfmaFormTable[r.form].name;
             d["m"] = r.m;
             d["n"] = r.n;
             d["k"] = r.k;
             d["bytes"] = r.bytes;
+            if (is_mxgemm(r.kind)) d["scale_bytes"] = r.scale_bytes;
             d["passes"] = r.passes;
             d["checksum"] = r.checksum;
             d["load_bytes_per_launch"] = r.load_bytes_per_launch;
@@ -1493,7 +2013,8 @@ void register_cotenant(py::module_& m) {
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
-      "\"cache\", \"chase\", \"mfma\" or \"gemm\", anything else raises ValueError "
+      "\"cache\", \"chase\", \"mfma\", \"gemm\", \"gemm-mxfp8\" or \"gemm-mxfp4\", anything "
+      "else raises ValueError "
       "before the device is touched. After one untimed "
       "launch, `launches` (1..64) launches of the same work run back to back "
       "on one stream, each between its own pair of events; the grid is 32 x "
@@ -1675,10 +2196,44 @@ void register_cotenant(py::module_& m) {
       "global loads ask for, work_per_launch = 2 M N K passes flops, rates "
       "in GFLOP/s, and clock_ghz per launch and as the median. It takes no "
       "form but \"bf16\" and no operands but \"registers\".\n\n"
+      "gemm-mxfp8, gemm-mxfp4: the same GEMM block-scaled, e4m3 bytes or e2m1 "
+      "nibbles (low first) under one E8M0 scale byte per row and block of 32 "
+      "k; grid, tile walk, work split, LDS layout, result, checksum rule and "
+      "clocks are gemm's, and neither takes a form or operands. `iters` is "
+      "the steps of 128 k (mxfp8; default 32, clamped to 1 .. 256) or 256 k "
+      "(mxfp4; default 16, clamped to 1 .. 64), a slab row of 128 bytes "
+      "either way; `bytes` is the elements of A plus B, 2 M K or M K, that is "
+      "256 M iters (0: M = 8192), M rounded down to a multiple of 128 and "
+      "clamped to 128 .. 32768; `passes` defaults to 32 and 64, a default "
+      "launch lasting about as long as gemm's. Elements are those of the "
+      "mfma forms at A(m % 192, k % 96) and B(k % 96, n % 192) under key = "
+      "mix32(seed32 ^ 0x47454D4D): mxfp8 hash % 15 - 7 with scale byte 127 + "
+      "e on both sides, mxfp4 the code hash & 15 with 128 + e for A and 128 "
+      "for B, e the scale bit of block (k % 96) // 32; every effective "
+      "element is an integer, |a b| <= 196 and 288, so K <= 32768 and 16384 "
+      "keep every sum below 2^23 and exact. The scales lie step-major, per "
+      "operand [iters][M] words of 4 or 8 bytes, byte b the step's block b, "
+      "so the 32 rows of a fragment are 128 or 256 contiguous bytes. A step "
+      "is 8 (mxfp8) or 16 (mxfp4) v_mfma_scale_f32_32x32x64_f8f6f4 per wave; "
+      "a fragment is read from LDS as chunk 4 s + h and 4 s + 2 + h (mxfp8) "
+      "or 2 s + h (mxfp4) of sub-step s, conflict-free ds_read_b128 as for "
+      "gemm. Two slabs are in flight: the loads of step i + 2 are issued at "
+      "the top of step i into one of two register sets and written to LDS "
+      "at the end of step i + 1, one barrier per step; the step's scale words "
+      "go from memory to registers at the same distance, never through LDS, "
+      "are shifted by 8 h once and picked per sub-step by the scale "
+      "operand's op_sel. All loads are buffer loads; past the last step they "
+      "are sent outside the buffer's range and read nothing. The result adds "
+      "form (\"mxfp8\" or \"mxfp4\") after workgroups and scale_bytes = 2 "
+      "iters M x 4 or 8 after bytes; load_bytes_per_launch = tiles * passes * "
+      "iters * (32768 + 4 * 128 * 4 or 8), slabs plus every wave's scale "
+      "words; the free-memory refusal counts bytes + scale_bytes; checksum "
+      "equals gemm_checksum(..., form=).\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
-      "{kind, [form,] applied_mask, tick_hz, workgroups, iters | [m, n, k,] bytes, passes, "
+      "{kind, [form,] applied_mask, tick_hz, workgroups, iters | [m, n, k,] bytes, "
+      "[scale_bytes,] passes, "
       "checksum, [load_bytes_per_launch,] "
       "[operands, lds_bytes, lds_bytes_per_launch,] "
       "[bytes_per_cu,] work_per_launch: flops, bytes or hops, launches: [{t0, t1, "
