@@ -438,7 +438,7 @@ class NodeAgent:
         containers are wired: each tenant's FMA and HBM-stream rate alone and
         while the other runs (cotenancy.isolation_report, to which `window`
         is passed: pairs, launches, iters, bytes, passes, timeout, windows,
-        form, operands).
+        form, operands, loads).
         Returns that report plus "tenants": [{core, mask, cus}].
 
         pairs=cotenancy.CACHE_PAIRS brings in the third kind, a tenant that
@@ -468,7 +468,12 @@ class NodeAgent:
         travel global memory -> LDS -> MFMA, with a window of bytes (A plus
         B), iters (steps of 64 k) and passes (GEMMs per launch); its entries
         carry the clock and its split as the mfma kind's do, and it takes
-        neither form nor operands. pairs=cotenancy.mxgemm_pairs("gemm-mxfp8"
+        neither form nor operands. loads= (one of cotenancy.GEMM_LOADS:
+        "registers", "direct") says how the gemm tenants get their slabs
+        into LDS: "direct" makes them load straight from memory into a ring
+        of LDS buffers, with no register in between, as production GEMMs on
+        gfx950 do; their entries then add "loads".
+        pairs=cotenancy.mxgemm_pairs("gemm-mxfp8"
         | "gemm-mxfp4") puts the block-scaled GEMM in its place, e4m3 or
         e2m1 elements under E8M0 scales per block of 32 k, steps of 128 or
         256 k; the form is the kind's name, so these take neither either.

@@ -50,7 +50,11 @@ the launch must sum to, in integers and in closed form. Like mfma it
 reports the clock it saw, so a pair splits its ratio the same way: beside
 a streamer both the chip-wide clock and the shared memory path move, and
 cycle_ratio is the part that is not the clock. It takes no form and no
-operands.
+operands. Its slabs reach LDS in one of two ways (GEMM_LOADS): "registers",
+global_load into registers and ds_write from them, or "direct", the
+16-byte LDS-DMA load of gfx950 that production GEMMs there use, a ring of
+slab pairs in LDS and no register in between. The product, and so the
+checksum, is the same.
 
 Two more kinds, "gemm-mxfp8" and "gemm-mxfp4" (MXGEMM_KINDS, TENANT_KINDS,
 mxgemm_pairs()), are that GEMM in the forms inference tenants run: e4m3 or
@@ -320,14 +324,18 @@ def _mfma_lane_sums(seed32: int, form: int = 0) -> Tuple[Tuple[int, ...], ...]:
     return tuple(out)
 
 
-# What an mfma tenant may be told beyond its window, in the order its child
-# is told, each with the values it may take.
-_MFMA_OPTIONS = {"form": MFMA_FORMS, "operands": MFMA_OPERANDS}
+# How a gemm tenant's slabs reach LDS: through registers, or straight from
+# memory with the LDS-DMA load.
+GEMM_LOADS = ("registers", "direct")
+# What an mfma or a gemm tenant may be told beyond its window, in the order
+# its child is told, each with the values it may take and the kinds it is for.
+_MFMA_OPTIONS = {"form": MFMA_FORMS, "operands": MFMA_OPERANDS, "loads": GEMM_LOADS}
+_OPTION_KINDS = {"form": MATRIX_KINDS, "operands": MATRIX_KINDS, "loads": GEMM_KINDS}
 
 
 def _checked(key: str, value: Optional[str]) -> str:
     if value not in _MFMA_OPTIONS[key]:
-        raise ValueError(f"unknown mfma {key} {value!r}: one of "
+        raise ValueError(f"unknown {_OPTION_KINDS[key][0]} {key} {value!r}: one of "
                          + ", ".join(_MFMA_OPTIONS[key]))
     return value
 
@@ -337,7 +345,7 @@ def _mfma_option(key: str, tenant: Mapping[str, Any], kind: str,
     """The option `key` that `tenant`, run as `kind`, is started with: its
     own, else the call-wide `wide`; None when neither names one."""
     own = tenant.get(key)
-    if kind not in MATRIX_KINDS:
+    if kind not in _OPTION_KINDS[key]:
         if own is not None:
             raise ValueError(f"a {kind} tenant takes no {key}: {own!r}")
         return None
@@ -488,6 +496,7 @@ def _child_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--form", choices=MFMA_FORMS, default="bf16")
     p.add_argument("--operands", choices=MFMA_OPERANDS, default=None)
+    p.add_argument("--loads", choices=GEMM_LOADS, default=None)
     return p
 
 
@@ -511,6 +520,9 @@ def child_main(argv: Optional[Sequence[str]] = None, stdin=None, stdout=None) ->
     # beside another kind.
     if args.operands is not None:
         window["operands"] = args.operands
+    # And the gemm kind's loads: the probe refuses "direct" beside another kind.
+    if args.loads is not None:
+        window["loads"] = args.loads
     warm = probe.cu_tenant_run(args.device, None, launches=1, **window)
     if "skipped" in warm:
         print(f"cotenancy child: {warm}", file=sys.stderr)
@@ -605,7 +617,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
              timeout: float = 120.0,
              spawn: Optional[Callable[[List[str], Dict[str, str]], Any]] = None,
              form: Optional[str] = None,
-             operands: Optional[str] = None) -> Dict[str, Any]:
+             operands: Optional[str] = None,
+             loads: Optional[str] = None) -> Dict[str, Any]:
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
     "fma" | "stream" | "cache" | "chase" | "mfma" | "gemm" | "gemm-mxfp8" |
@@ -629,6 +642,14 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     for it. A gemm, gemm-mxfp8 or gemm-mxfp4 tenant is of another kind in
     this sense: it takes neither.
 
+    `loads` (one of GEMM_LOADS) says how every gemm tenant of the call gets
+    its slabs into LDS, by the same rules again: a gemm tenant may carry its
+    own "loads" instead, an unknown value or "loads" on a tenant of any
+    other kind (gemm-mxfp8 and gemm-mxfp4 included) raises ValueError before
+    anything is started, the call-wide value leaves the other kinds as they
+    are, and a child is given --loads, after --operands, only when one was
+    named for it.
+
     Each child has `timeout` seconds from its start. The first child that
     times out, exits non-zero or prints no TENANT line ends the run: the
     others are killed and {"ok": False, "reason": "child-failed", "detail"}
@@ -637,7 +658,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
         raise ValueError("run_pair takes one or two tenants")
     if kinds is not None and len(kinds) != len(tenants):
         raise ValueError("one kind per tenant")
-    call = {"form": form, "operands": operands}
+    call = {"form": form, "operands": operands, "loads": loads}
     for key, value in call.items():
         if value is not None:
             _checked(key, value)
@@ -729,9 +750,10 @@ _SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",), "gemm": ("clock_
 
 
 def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
-              operands=None) -> Optional[int]:
+              operands=None, loads=None) -> Optional[int]:
     """The checksum a child's result must carry by the oracle of its kind
-    (`pattern` is the reading kinds'); None for a kind that has none."""
+    (`pattern` is the reading kinds'); None for a kind that has none. A gemm
+    tenant's `loads` do not enter it: the product is the same."""
     kind = result["kind"]
     if kind in READING_KINDS:
         return pattern(seed, int(result["bytes"]))
@@ -756,7 +778,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                      expected_checksum: Optional[Callable[[int, int], int]] = None,
                      windows: Optional[Mapping[str, Mapping[str, int]]] = None,
                      form: Optional[str] = None,
-                     operands: Optional[str] = None) -> Dict[str, Any]:
+                     operands: Optional[str] = None,
+                     loads: Optional[str] = None) -> Dict[str, Any]:
     """Each of two tenants' ({"mask": int}) rate alone and next to the other.
 
     First one solo run per tenant and kind that `pairs` uses, then the pairs
@@ -826,6 +849,15 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     named anywhere the children are started as before, keep their operands
     in registers, and no entry has "operands".
 
+    `loads` (one of GEMM_LOADS, anything else raises ValueError) says how
+    the gemm tenants get their slabs into LDS, alone and in every pair:
+    "registers", or "direct" for tenants that load them straight from
+    memory into a ring of LDS buffers; a tenant ({"mask": int, "loads":
+    str}) may name its own instead. The other kinds are not touched by it.
+    The checksum stays gemm_checksum()'s, and the gemm entries, solo and in
+    a pair, add "loads". With none named anywhere the children are started
+    as before and no entry has "loads".
+
     ok says that the measurement is valid (every child exited 0, every
     stream and cache checksum equals the pattern's, every chase, mfma and
     gemm checksum the closed form's, overlap was reached), not that the
@@ -842,9 +874,10 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     for kind, w in windows.items():
         if kind not in TENANT_KINDS or any(k not in WINDOW_KEYS for k in w):
             raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
-    # Per option and tenant, what the tenant is started with as an mfma one.
-    named = {key: [_mfma_option(key, t, MATRIX_KINDS[0], wide) for t in tenants]
-             for key, wide in (("form", form), ("operands", operands))}
+    # Per option and tenant, what the tenant is started with as a tenant of
+    # the option's kind.
+    named = {key: [_mfma_option(key, t, _OPTION_KINDS[key][0], wide) for t in tenants]
+             for key, wide in (("form", form), ("operands", operands), ("loads", loads))}
     # The pattern's oracle, asked once per size.
     pattern = functools.lru_cache(maxsize=None)(expected_checksum or _pattern_checksum)
     window = {"iters": iters, "bytes": bytes, "passes": passes, "seed": seed,

@@ -28,7 +28,9 @@ FP8 or block-scaled MX instructions in place of the bf16 one, and
 --co-tenancy-mfma-operands lds with its operands re-read from LDS every step.
 --co-tenancy-gemm does it for the tenant all of those lead up to: a whole
 bf16 GEMM whose operands travel global memory -> LDS -> MFMA;
---co-tenancy-gemm-form runs that GEMM block-scaled, MXFP8 or MXFP4.
+--co-tenancy-gemm-form runs that GEMM block-scaled, MXFP8 or MXFP4, and
+--co-tenancy-gemm-loads direct the bf16 one with its slabs loaded straight
+from memory into LDS.
 """
 from __future__ import annotations
 
@@ -180,6 +182,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "the kinds gemm-mxfp8 and gemm-mxfp4 in place of "
                         "gemm in every pair; one report per card and form, "
                         "one after another")
+    p.add_argument("--co-tenancy-gemm-loads", choices=("registers", "direct"),
+                   default=None,
+                   help="with --co-tenancy-gemm: how the GEMM tenants get "
+                        "their slabs into LDS: registers (what they do when "
+                        "the flag is absent), or direct, loaded from memory "
+                        "straight into a ring of LDS buffers as production "
+                        "GEMMs on gfx950 do; not together with "
+                        "--co-tenancy-gemm-form, whose kinds have no such "
+                        "path")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -217,7 +228,9 @@ def main(argv=None) -> int:
             ("--co-tenancy-mfma-operands", "--co-tenancy-mfma", ()),
             ("--co-tenancy-gemm", "--co-tenancy",
              ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma")),
-            ("--co-tenancy-gemm-form", "--co-tenancy-gemm", ())):
+            ("--co-tenancy-gemm-form", "--co-tenancy-gemm", ()),
+            ("--co-tenancy-gemm-loads", "--co-tenancy-gemm",
+             ("--co-tenancy-gemm-form",))):
         if not given(flag):
             continue
         if not given(needs):
@@ -240,6 +253,8 @@ def main(argv=None) -> int:
                     for form in args.co_tenancy_gemm_form}
         elif args.co_tenancy_gemm:
             common = {"pairs": GEMM_PAIRS}
+            if args.co_tenancy_gemm_loads is not None:
+                common["loads"] = args.co_tenancy_gemm_loads
         elif args.co_tenancy_mfma:
             common = {"pairs": MFMA_PAIRS}
             if args.co_tenancy_mfma_operands is not None:

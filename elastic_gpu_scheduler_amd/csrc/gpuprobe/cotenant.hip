@@ -1482,6 +1482,207 @@ tenant_mxgemm_kernel(const int4v* __restrict__ a, const int4v* __restrict__ b,
   clocked_end(rec, clk, c0, t0);
 }
 
+// ---- gemm, loads straight to LDS ---------------------------------------------
+
+// How many {A slab, B slab} pairs the ring of tenant_gemm_direct_kernel holds:
+// 2 (64 KiB of slabs, two workgroups per CU) unless GPUPROBE_GEMM_DIRECT_STAGES
+// is defined as 3 (96 KiB, one workgroup per CU), the depth the kept one was
+// measured against (profiles/gemm_direct_cotenancy_results.md: on the whole
+// card two pairs run 1.29-1.30 PFLOP/s at 47.7-47.9 cycles per MFMA and SIMD,
+// three 1.03-1.04 at 75.3-76.0, beside 1.05-1.07 at 69.9-70.8 for the
+// kernel that stages through registers, the same command repeated moving
+// each by about 1 %. A second workgroup on the CU hides a barrier and the
+// reads behind it; a deeper ring that costs that workgroup does not.)
+#ifndef GPUPROBE_GEMM_DIRECT_STAGES
+#define GPUPROBE_GEMM_DIRECT_STAGES 2
+#endif
+constexpr int kGemmDirectStages = GPUPROBE_GEMM_DIRECT_STAGES;
+static_assert(kGemmDirectStages == 2 || kGemmDirectStages == 3, "a ring of two or three");
+
+using LdsPtr = __attribute__((address_space(3))) void*;
+
+// One step's sixteen MFMAs of a wave on the slabs {A, B} of `from`: the
+// `multiply` of tenant_gemm_kernel as a function (that kernel keeps its own,
+// so that its code stays the one its figures were measured on). The lane
+// reads rows read_a / 8 and read_b / 8 (+ 32 t) of the slabs, chunk (2 s + h)
+// ^ read_key at sub-step s.
+__device__ inline void gemm_multiply(MfmaTile& acc, const int4v (*from)[kGemmSlabVecs],
+                                     uint32_t read_a, uint32_t read_b, uint32_t read_key,
+                                     uint32_t h) {
+  const auto read = [&](MfmaFrags<kBf16>& f, uint32_t s) {
+    const uint32_t c = (2 * s + h) ^ read_key;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f.a[t] = __builtin_bit_cast(bf16x8, from[0][read_a + 32 * kGemmRowVecs * t + c]);
+      f.b[t] = __builtin_bit_cast(bf16x8, from[1][read_b + 32 * kGemmRowVecs * t + c]);
+    }
+  };
+  MfmaFrags<kBf16> f[2];
+  read(f[0], 0);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (uint32_t s = 0; s < 4; ++s) {
+    if (s < 3) read(f[(s + 1) & 1u], s + 1);
+    mfma_step(f[s & 1u], acc);
+    if (s < 3) mfma_lds_interleave<4, 2>();
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// tenant_gemm_kernel's product from the same buffers with the slabs loaded
+// global memory -> LDS without passing through registers (the 16-byte LDS-DMA
+// load of gfx950, buffer_load_dwordx4 ... lds), as production GEMMs on this
+// chip feed their LDS. Fill, grid, tile walk (gemm_order), work split, K-step,
+// LDS layout as the reading side sees it (gemm_slot), the fragment reads
+// (gemm_multiply), exactness, result, stamps and clocks are
+// tenant_gemm_kernel's; what follows is this kernel's own.
+//
+// Where the swizzle lives. An LDS-DMA load writes lane l's 16 bytes to (a
+// wave-uniform base, in m0) + 16 l: one wave instruction fills 64 consecutive
+// chunk positions, eight whole slab rows, and no lane chooses where its data
+// lands. The readers still find chunk c of row R at position c ^ q(R)
+// (gemm_slot, so its bank argument for ds_read_b128 holds unchanged); hence
+// the lane that lands on position p of row R fetches chunk p ^ q(R) of that
+// row from memory. Wave w's instruction i (0..3) fills rows 32 i + 8 w .. + 7
+// of a slab, lane l on row R = 32 i + 8 w + (l >> 3) at position l & 7. q(R) =
+// (R & 6) | ((R >> 3) & 1) = ((l >> 3) & 6) | (w & 1): 32 i and 8 w leave bits
+// 1 and 2 alone, and bit 3 of R is bit 0 of w, as l >> 3 < 8 carries nothing
+// into it. The key does not depend on i, so a lane's offset into the matrix
+// is computed once, before the start stamp. Eight lanes still read one row's
+// 128 contiguous bytes of the step, permuted. Four loads per lane, operand
+// and step, eight in all; no ds_write, and no registers hold a slab.
+//
+// Ring and wait. LDS holds D = kGemmDirectStages pairs {A slab, B slab}. Step
+// i issues the loads of step i + D - 1 into pair (i + D - 1) % D, multiplies
+// from pair i % D, waits for s_waitcnt vmcnt(8 (D - 2)) and crosses one
+// barrier. Nothing makes a wave wait for what the other waves loaded but
+// this count: loads retire in issue order, a lane has issued eight per step,
+// so with at most 8 (D - 2) outstanding everything up to the loads of step i
+// + 1 has landed, and behind the barrier that holds for every wave. With D =
+// 3 the loads of step i + 2 stay in flight across the barrier, which a
+// kernel that stages through registers cannot express: its ds_write needs
+// the data. The pair overwritten in step i, (i - 1) % D, was last read in
+// step i - 1, and every wave left that step through its barrier after its
+// MFMAs had consumed what it read. The prologue issues steps 0 .. D - 2 and
+// waits with the same count: of its 8 (D - 1) loads the first eight, step
+// 0's, have landed. Every step, the last D - 1 included, issues its eight
+// loads (see Bounds), so the count means the same in every step; behind the
+// loop vmcnt(0) lets nothing land after the reduction has begun.
+//
+// Bounds. Buffer loads on a descriptor that covers exactly the tile's 128
+// rows of the operand, at most 128 x 65536 bytes: a lane's offset is (8 w +
+// (l >> 3)) x row bytes + 16 x chunk, the shared one 32 i x row bytes + 128 x
+// step, together row x row bytes + 128 step + 16 chunk with row < 128, step <
+// steps, chunk < 8, so the 16 bytes end at or before the window's end, which
+// is inside the matrix. Chosen over a branch around the loads because the
+// wait count then never changes: a load of a step past the last (steps < D -
+// 1 in the prologue, the last D - 1 steps of the loop) is issued with bit 31
+// set in every lane's offset, outside any window, which the hardware answers
+// without reading memory; what it leaves in LDS lies in a pair nobody reads
+// again. No load and no barrier has a branch around it but the loop's own,
+// whose count is the workgroup's. The LDS address handed to a load is
+// computed from the wave's number, made a scalar with readfirstlane, and
+// constants: wave-uniform by construction. An LDS address is pair x 32 KiB +
+// operand x 16 KiB + (32 i + 8 w) x 128 + 16 l + 15 < D x 32 KiB.
+//
+// The loads are written as assembly, not as the compiler's
+// raw_ptr_buffer_load_lds builtin: behind the builtin the compiler puts
+// s_waitcnt vmcnt(0) in front of the first LDS read that follows and in front
+// of the barrier, which takes the loads out of flight at once; the assembly
+// it knows only as something that touches memory, and the counted wait above
+// is the only one.
+//
+// No FP32 arithmetic but the MFMAs' is written here.
+//
+// hipcc -O3 for gfx950 reports (-Rpass-analysis=kernel-resource-usage), D = 2
+// and D = 3: 170 VGPRs and no AGPRs, 168 VGPRs and 64 AGPRs (the
+// accumulators), 42 SGPRs, no scratch and no spills, 67584 and 100352 bytes
+// of LDS and an occupancy of 2 and 1 waves per SIMD, by LDS in either case.
+// tenant_gemm_kernel and both tenant_mxgemm_kernels report what they did
+// before this kernel was added.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"  // m0 is clobbered on purpose
+template <int D>
+__global__ void __launch_bounds__(kBlock, D == 2 ? 2 : 1)
+tenant_gemm_direct_kernel(const int4v* __restrict__ a, const int4v* __restrict__ b,
+                          uint32_t side, uint32_t steps, unsigned long long* __restrict__ out,
+                          unsigned long long* __restrict__ rec,
+                          unsigned long long* __restrict__ clk) {
+  __shared__ int4v slab[D][2][kGemmSlabVecs];  // [pair][A, B]
+  __shared__ unsigned long long sums[kBlock];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = lane & 31u, h = lane >> 5;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+  const uint32_t tiles = side * side;
+  const uint32_t tile = gemm_order(blockIdx.x % tiles, tiles, side);
+  const uint32_t row0 = (tile >> 16) * kGemmTile, col0 = (tile & 0xFFFFu) * kGemmTile;
+  // What this lane loads: of rows 8 wave + (lane >> 3) + 32 i the chunk that
+  // belongs at position lane & 7.
+  const uint32_t row_bytes = steps * (kGemmRowVecs * 16);
+  const uint32_t load_key = ((lane >> 3) & 6u) | (wave & 1u);
+  const uint32_t load_at = (8 * wave + (lane >> 3)) * row_bytes + 16 * ((lane & 7u) ^ load_key);
+  const uint32_t land_at = 8 * wave * kGemmRowVecs;  // + 32 rows: + 256
+  // The descriptor's four words, written out because an asm operand takes
+  // them as a vector: base, base's high 16 bits with stride 0, bytes, word 3.
+  const auto window = [&](const int4v* first) {
+    const uint64_t base = reinterpret_cast<uint64_t>(first);
+    return int4v{static_cast<int>(static_cast<uint32_t>(base)),
+                 static_cast<int>(static_cast<uint32_t>(base >> 32) & 0xFFFFu),
+                 static_cast<int>(kGemmTile * row_bytes), kBufferWord3};
+  };
+  const auto ra = window(a + static_cast<uint64_t>(row0) * (row_bytes / 16));
+  const auto rb = window(b + static_cast<uint64_t>(col0) * (row_bytes / 16));
+  const uint32_t read_a = (64 * (wave >> 1) + r) * kGemmRowVecs;
+  const uint32_t read_b = (64 * (wave & 1u) + r) * kGemmRowVecs;
+  const uint32_t read_key = gemm_key(r);
+
+  // One load: m0 = the LDS address of the wave's 1 KiB, a wait state that a
+  // write of m0 needs before an LDS-DMA load reads it, the load.
+  const auto load = [](int4v rsrc, const int4v* lds, uint32_t lane_off, uint32_t shared_off)
+      __attribute__((always_inline)) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+                 :
+                 : "s"(static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsPtr)lds))),
+                   "v"(lane_off), "s"(rsrc), "s"(shared_off)
+                 : "memory", "m0");
+  };
+  // The eight loads of step `at_step` into the pair `to`.
+  const auto issue = [&](const int4v (*to)[kGemmSlabVecs], uint32_t at_step)
+      __attribute__((always_inline)) {
+    const uint32_t at = load_at | (at_step < steps ? 0u : kBufferOutside);
+    const uint32_t slab_off = at_step * (kGemmRowVecs * 16);
+#pragma unroll
+    for (int i = 0; i < kGemmLoads; ++i) {
+      load(ra, to[0] + land_at + 32 * kGemmRowVecs * i, at, slab_off + 32 * i * row_bytes);
+      load(rb, to[1] + land_at + 32 * kGemmRowVecs * i, at, slab_off + 32 * i * row_bytes);
+    }
+  };
+  // At most 8 (D - 2) of this wave's loads still outstanding, then the barrier.
+  const auto landed = [] {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kGemmLoads * (D - 2)) : "memory");
+    __syncthreads();
+  };
+  f32x16 acc[2][2];
+
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  const unsigned long long t0 = stamp_start();
+  mfma_zero(acc);
+  for (uint32_t i = 0; i + 1 < D; ++i) issue(slab[i], i);
+  landed();
+  uint32_t from = 0, to = D - 1;  // i % D and (i + D - 1) % D
+  for (uint32_t i = 0; i < steps; ++i) {
+    issue(slab[to], i + D - 1);
+    gemm_multiply(acc, slab[from], read_a, read_b, read_key, h);
+    landed();
+    to = from;
+    from = from + 1 == D ? 0 : from + 1;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  gemm_store_sum(sums, gemm_tile_sum(acc, row0, col0, wave, r, h), out);
+  clocked_end(rec, clk, c0, t0);
+}
+#pragma clang diagnostic pop
+
 // ---- host ------------------------------------------------------------------
 
 enum class Kind : int { kFma, kStream, kCache, kChase, kMfma, kGemm, kGemmMxfp8, kGemmMxfp4 };
@@ -1546,6 +1747,7 @@ struct TenantResult {
   int form = kBf16;  // mfma, and the block-scaled gemms, whose kind names it
   bool lds = false;  // mfma only: operands re-read from LDS
   uint64_t lds_bytes = 0, lds_bytes_per_launch = 0;  // mfma from LDS only
+  bool direct = false;  // gemm only: slabs loaded straight to LDS; sets lds_bytes too
   MaskWords applied;
   double tick_hz = 0.0;
   int workgroups = 0;
@@ -1574,11 +1776,12 @@ struct TenantResult {
 // process started under ROC_GLOBAL_CU_MASK the runtime reports only that mask's
 // CUs, so there the grid is 32 x its own CUs; every rate is over the work launched.)
 TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int passes,
-                         int form, bool lds) {
+                         int form, bool lds, bool direct) {
   TenantResult r;
   r.kind = kind;
   r.form = form;
   r.lds = lds;
+  r.direct = direct;
   r.workgroups = kKindTable[static_cast<int>(kind)].groups_per_cu * cus;
   const double lanes = static_cast<double>(r.workgroups) * kBlock;
   const uint64_t waves = static_cast<uint64_t>(r.workgroups) * kWavesPerGroup;
@@ -1638,6 +1841,8 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
       r.work_per_launch = 2.0 * r.m * r.n * r.k * r.passes;
       r.load_bytes_per_launch =
           static_cast<uint64_t>(r.workgroups) * 2 * kGemmTile * r.k * 2;
+      if (direct)  // the ring of slab pairs and the reduction's words
+        r.lds_bytes = kGemmDirectStages * 2 * kGemmSlabVecs * 16 + kBlock * 8;
       break;
     }
     case Kind::kGemmMxfp8:
@@ -1742,7 +1947,8 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
              rec, clks.at(2 * slot));
           break;
         case Kind::kGemm:  // A, then B behind it
-          go(grid, tenant_gemm_kernel, buf.as<const int4v>(), buf.as<const int4v>() + n16 / 2,
+          go(grid, r.direct ? tenant_gemm_direct_kernel<kGemmDirectStages> : tenant_gemm_kernel,
+             buf.as<const int4v>(), buf.as<const int4v>() + n16 / 2,
              static_cast<uint32_t>(r.side), static_cast<uint32_t>(r.iters), o64, rec,
              clks.at(2 * slot));
           break;
@@ -1859,13 +2065,13 @@ void summarise(TenantResult& r) {
 
 TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int launches,
                         int iters, uint64_t bytes, int passes, uint64_t seed, int form,
-                        bool lds) {
+                        bool lds, bool direct) {
   require_device(device);
   const int cus = gpuprobe::device_cus(device);
   const MaskWords mask =
       raw_mask.empty() ? MaskWords{} : gpuprobe::fit_mask(raw_mask, cus);
   launches = std::min(std::max(launches, 1), kMaxLaunches);
-  TenantResult r = plan_tenant(kind, cus, iters, bytes, passes, form, lds);
+  TenantResult r = plan_tenant(kind, cus, iters, bytes, passes, form, lds, direct);
   if (kKindTable[static_cast<int>(kind)].reads) {
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
@@ -1892,7 +2098,7 @@ void register_cotenant(py::module_& m) {
       "cu_tenant_run",
       [](int device, py::object mask, const std::string& kind, int launches, int iters,
          uint64_t bytes, int passes, uint64_t seed, const std::string& form,
-         const std::string& operands) {
+         const std::string& operands, const std::string& loads) {
         const MaskWords words = gpuprobe::mask_from_python(mask);
         int k = 0;
         while (k < kKinds && kind != kKindTable[k].name) ++k;
@@ -1918,11 +2124,18 @@ void register_cotenant(py::module_& m) {
           throw py::value_error(
               "cu_tenant_run: operands \"lds\" needs kind \"mfma\"; of the operands "
               "\"registers\" and \"lds\" every other kind takes only \"registers\"");
+        if (loads != "registers" && loads != "direct")
+          throw py::value_error("cu_tenant_run: loads must be \"registers\" or \"direct\"");
+        const bool direct = loads == "direct";
+        if (direct && static_cast<Kind>(k) != Kind::kGemm)
+          throw py::value_error(
+              "cu_tenant_run: loads \"direct\" needs kind \"gemm\"; of the loads "
+              "\"registers\" and \"direct\" every other kind takes only \"registers\"");
         TenantResult r;
         {
           py::gil_scoped_release release;
           r = run_tenant(device, words, static_cast<Kind>(k), launches, iters, bytes,
-                         passes, seed, f, lds);
+                         passes, seed, f, lds, direct);
         }
         py::dict d;
         if (r.skipped) {
@@ -1981,6 +2194,11 @@ void register_cotenant(py::module_& m) {
             d["passes"] = r.passes;
             d["checksum"] = r.checksum;
             d["load_bytes_per_launch"] = r.load_bytes_per_launch;
+            if (r.direct) {
+              d["loads"] = loads;
+              d["stages"] = kGemmDirectStages;
+              d["lds_bytes"] = r.lds_bytes;
+            }
             clocks = true;
             last["clock_ghz"] = r.clock_ghz;
             break;
@@ -2009,7 +2227,7 @@ void register_cotenant(py::module_& m) {
       py::arg("device") = 0, py::arg("mask") = py::none(), py::arg("kind") = "fma",
       py::arg("launches") = 8, py::arg("iters") = 0, py::arg("bytes") = 0,
       py::arg("passes") = 0, py::arg("seed") = 1, py::arg("form") = "bf16",
-      py::arg("operands") = "registers",
+      py::arg("operands") = "registers", py::arg("loads") = "registers",
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
@@ -2196,6 +2414,25 @@ void register_cotenant(py::module_& m) {
       "global loads ask for, work_per_launch = 2 M N K passes flops, rates "
       "in GFLOP/s, and clock_ghz per launch and as the median. It takes no "
       "form but \"bf16\" and no operands but \"registers\".\n\n"
+      "gemm, `loads`: \"registers\" (the default, everything above) or "
+      "\"direct\"; anything else, or \"direct\" with a kind other than "
+      "\"gemm\", raises ValueError before the device is touched. With "
+      "\"direct\" the same product is computed from the same buffers, but "
+      "the slabs go from memory straight to LDS (buffer_load_dwordx4 ... "
+      "lds, 16 bytes per lane) and pass through no register: such a load "
+      "puts lane l's bytes at a wave-uniform LDS address + 16 l, so the XOR "
+      "of the LDS layout is applied to the address in memory instead (the "
+      "lane that lands on position p of row R fetches chunk p ^ key(R)) and "
+      "the fragment reads stay as they are. LDS holds a ring of `stages` "
+      "slab pairs (2 as built; 3 with GPUPROBE_GEMM_DIRECT_STAGES=3); step i "
+      "issues the loads of step i + stages - 1, multiplies, waits until at "
+      "most 8 (stages - 2) of its loads are outstanding and crosses one "
+      "barrier, so with three stages a step's loads stay in flight across a "
+      "barrier. All loads are buffer loads on a descriptor of the tile's 128 "
+      "rows; past the last step they are sent outside it and read nothing. "
+      "The result adds loads, stages and lds_bytes (per workgroup: stages x "
+      "32 KiB + 2 KiB) after load_bytes_per_launch; with \"registers\" it "
+      "has none of the three. The checksum is gemm_checksum's either way.\n\n"
       "gemm-mxfp8, gemm-mxfp4: the same GEMM block-scaled, e4m3 bytes or e2m1 "
       "nibbles (low first) under one E8M0 scale byte per row and block of 32 "
       "k; grid, tile walk, work split, LDS layout, result, checksum rule and "
@@ -2234,7 +2471,7 @@ void register_cotenant(py::module_& m) {
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
       "{kind, [form,] applied_mask, tick_hz, workgroups, iters | [m, n, k,] bytes, "
       "[scale_bytes,] passes, "
-      "checksum, [load_bytes_per_launch,] "
+      "checksum, [load_bytes_per_launch, [loads, stages, lds_bytes,]] "
       "[operands, lds_bytes, lds_bytes_per_launch,] "
       "[bytes_per_cu,] work_per_launch: flops, bytes or hops, launches: [{t0, t1, "
       "seconds: (t1 - t0) "
