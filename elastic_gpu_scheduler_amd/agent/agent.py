@@ -477,6 +477,13 @@ class NodeAgent:
         | "gemm-mxfp4") puts the block-scaled GEMM in its place, e4m3 or
         e2m1 elements under E8M0 scales per block of 32 k, steps of 128 or
         256 k; the form is the kind's name, so these take neither either.
+        pairs=cotenancy.decode_pairs("decode-mxfp8" | "decode-mxfp4") brings
+        in the decode shape of that GEMM, 32 token rows against a weight
+        matrix streamed from memory once per pass (window: bytes of W,
+        iters, passes = re-reads of W), beside itself, the streamer and the
+        prefill gemm kind, both ways round: the tenant that loads the
+        matrix cores and HBM together. Its entries carry the clock and its
+        split too, and it takes neither form nor operands nor loads.
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched

@@ -64,6 +64,21 @@ flight. The form is part of the kind's name, so they too take neither form
 nor operands; their window is the gemm kind's with a step of 128 or 256 k,
 and gemm_shape() and gemm_checksum() take the form as a keyword.
 
+Two more again, "decode-mxfp8" and "decode-mxfp4" (DECODE_KINDS, CO_KINDS,
+decode_pairs()), are the other shape of the same block-scaled GEMM, the one
+an inference tenant spends most of its time in: 32 token rows against a
+weight matrix that is read once, C (32 x N) = A (32 x K) . W^T. Every byte
+of W is used for 32 rows and never again, so HBM sets the pace and not the
+matrix pipe: the one tenant that loads the matrix cores and the memory
+system together. W goes from memory straight to registers in fragment
+layout, several steps in flight per wave; the 32 rows of A are shared by a
+workgroup's waves through LDS. Their window is `bytes` (W's elements, 0: 1
+GiB, more than the Infinity Cache holds), `iters` (steps of 128 or 256 k, 0:
+K = 8192) and `passes` (whole re-reads of W); decode_shape() states the
+shape and gemm_checksum(32, n, k, ...) is the oracle unchanged. They take
+neither form nor operands nor loads. TENANT_KINDS stays the kinds before
+them; CO_KINDS is every kind a child can be started as.
+
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
 
@@ -121,6 +136,22 @@ def mxgemm_pairs(kind: str) -> Tuple[Tuple[str, str], ...]:
     if kind not in MXGEMM_KINDS:
         raise ValueError(f"not a block-scaled gemm kind: {kind!r}")
     return tuple(tuple(kind if k == "gemm" else k for k in pair) for pair in GEMM_PAIRS)
+
+
+# The kinds that are the decode shape of a block-scaled GEMM, the form in the
+# name; and every kind a tenant can be.
+DECODE_KINDS = ("decode-mxfp8", "decode-mxfp4")
+CO_KINDS = TENANT_KINDS + DECODE_KINDS
+DECODE_ROWS = 32  # rows of A
+
+
+def decode_pairs(kind: str) -> Tuple[Tuple[str, str], ...]:
+    """The pairs that say what a neighbour does to a decode tenant of `kind`
+    (one of DECODE_KINDS) and what it does to them: another such tenant, the
+    streamer both ways round, and the prefill bf16 GEMM both ways round."""
+    if kind not in DECODE_KINDS:
+        raise ValueError(f"not a decode kind: {kind!r}")
+    return ((kind, kind), (kind, "stream"), ("stream", kind), (kind, "gemm"), ("gemm", kind))
 
 
 # What may differ from tenant to tenant, or from kind to kind, within one call.
@@ -441,6 +472,21 @@ def gemm_shape(bytes: int = 0, iters: int = 0, form: str = "bf16") -> Tuple[int,
     return side, side, rule["step"] * steps
 
 
+def decode_shape(bytes: int = 0, iters: int = 0, form: str = "mxfp4") -> Tuple[int, int, int]:
+    """(32, n, k) of the GEMM a decode-mxfp8 or decode-mxfp4 tenant (`form`
+    "mxfp8" or "mxfp4") runs for the window keys `bytes` and `iters`, the
+    probe's rule stated on its own: k = 128 or 256 * iters (0: K = 8192;
+    clamped to 1 .. 256 or 1 .. 64 steps), and n = bytes // (128 * iters), W's
+    elements being 128 bytes per row and step in either form (0: 1 GiB),
+    rounded down to a multiple of 128 and clamped to 128 .. 2^20."""
+    rule = _gemm_form(form)
+    if not rule["scale_bytes"]:
+        raise ValueError(f"a decode tenant is block-scaled: {form!r}")
+    steps = min(int(iters), rule["max_iters"]) if int(iters) > 0 else 8192 // rule["step"]
+    n = (int(bytes) or 1 << 30) // (128 * steps) // GEMM_TILE * GEMM_TILE
+    return DECODE_ROWS, min(max(n, GEMM_TILE), 1 << 20), rule["step"] * steps
+
+
 def gemm_checksum(m: int, n: int, k: int, passes: int, seed: int,
                   form: str = "bf16") -> int:
     """What a gemm tenant's checksum must be, in integers and closed form. C
@@ -488,7 +534,7 @@ def _child_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="cotenancy", description=__doc__)
     p.add_argument("--child", action="store_true", required=True)
     p.add_argument("--device", type=int, default=0)
-    p.add_argument("--kind", choices=TENANT_KINDS, default="fma")
+    p.add_argument("--kind", choices=CO_KINDS, default="fma")
     p.add_argument("--launches", type=int, default=8)
     p.add_argument("--iters", type=int, default=0)
     p.add_argument("--bytes", type=int, default=0)
@@ -622,7 +668,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
     "fma" | "stream" | "cache" | "chase" | "mfma" | "gemm" | "gemm-mxfp8" |
-    "gemm-mxfp4"} and may carry its own "launches", "iters",
+    "gemm-mxfp4" | "decode-mxfp8" | "decode-mxfp4"} and may carry its
+    own "launches", "iters",
     "bytes" and "passes" in place of the call-wide ones; `kinds`, when given,
     names the kinds instead. Every child warms up and says READY; only then
     are all told GO. Returns {"ok": True, "tenants": [the children's
@@ -639,13 +686,14 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     carry its own "operands" instead, an unknown value or "operands" on a
     tenant of another kind raises ValueError before anything is started,
     and a child is given --operands, after --form, only when one was named
-    for it. A gemm, gemm-mxfp8 or gemm-mxfp4 tenant is of another kind in
-    this sense: it takes neither.
+    for it. A gemm, gemm-mxfp8, gemm-mxfp4 or decode tenant is of another
+    kind in this sense: it takes neither.
 
     `loads` (one of GEMM_LOADS) says how every gemm tenant of the call gets
     its slabs into LDS, by the same rules again: a gemm tenant may carry its
     own "loads" instead, an unknown value or "loads" on a tenant of any
-    other kind (gemm-mxfp8 and gemm-mxfp4 included) raises ValueError before
+    other kind (gemm-mxfp8, gemm-mxfp4 and the decode kinds included)
+    raises ValueError before
     anything is started, the call-wide value leaves the other kinds as they
     are, and a child is given --loads, after --operands, only when one was
     named for it.
@@ -674,7 +722,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     try:
         for i, tenant in enumerate(tenants):
             kind = kinds[i] if kinds is not None else tenant["kind"]
-            if kind not in TENANT_KINDS:
+            if kind not in CO_KINDS:
                 raise ValueError(f"unknown tenant kind {kind!r}")
             env = dict(os.environ)
             env[ENV_CU_MASK] = mask_hex(int(tenant["mask"]))
@@ -746,7 +794,7 @@ def _balanced(launches: int, seconds: Sequence[float]) -> List[int]:
 # What a report knows of each kind. First the keys of a child's result that a
 # solo entry adds; a kind that adds clock_ghz gets the clock split in a pair.
 _SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",), "gemm": ("clock_ghz",),
-              **{kind: ("clock_ghz",) for kind in MXGEMM_KINDS}}
+              **{kind: ("clock_ghz",) for kind in MXGEMM_KINDS + DECODE_KINDS}}
 
 
 def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
@@ -767,6 +815,9 @@ def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
     if kind in MXGEMM_KINDS:
         return gemm_checksum(result["m"], result["n"], result["k"], result["passes"], seed,
                              form=kind[len("gemm-"):])
+    if kind in DECODE_KINDS:
+        return gemm_checksum(result["m"], result["n"], result["k"], result["passes"], seed,
+                             form=kind[len("decode-"):])
     return None
 
 
@@ -831,6 +882,18 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     its split as a gemm tenant's do. It too takes neither `form` nor
     `operands`.
 
+    A decode-mxfp8 or decode-mxfp4 tenant (pairs=decode_pairs(kind)) is the
+    decode shape of that GEMM, 32 rows of A against a weight matrix W that
+    is streamed from memory once per pass: `bytes` are W's elements, `iters`
+    steps of 128 or 256 k, `passes` re-reads of W, see decode_shape(). Its
+    rates are GFLOP/s, 64 (mxfp8) or 128 (mxfp4) flop per byte of W, so rate
+    / 64 or / 128 is the GB/s of weights it streams; its checksum is held
+    against gemm_checksum(32, n, k, ..., form=), and its
+    entries carry the clock and its split as a gemm tenant's do: beside a
+    streamer or a prefill GEMM, clock_ratio is what the chip-wide clock took
+    and cycle_ratio what the shared memory path took. It takes neither
+    `form` nor `operands` nor `loads`.
+
     `form` (one of MFMA_FORMS, anything else raises ValueError) is the
     instruction the mfma tenants issue, alone and in every pair; a tenant
     ({"mask": int, "form": str}) may name its own instead, for a bf16 tenant
@@ -868,11 +931,11 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     if len(tenants) != 2:
         raise ValueError("isolation_report takes two tenants")
     for pair in pairs:
-        if len(pair) != 2 or any(k not in TENANT_KINDS for k in pair):
+        if len(pair) != 2 or any(k not in CO_KINDS for k in pair):
             raise ValueError(f"not a pair of tenant kinds: {pair!r}")
     windows = {kind: dict(w) for kind, w in (windows or {}).items()}
     for kind, w in windows.items():
-        if kind not in TENANT_KINDS or any(k not in WINDOW_KEYS for k in w):
+        if kind not in CO_KINDS or any(k not in WINDOW_KEYS for k in w):
             raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
     # Per option and tenant, what the tenant is started with as a tenant of
     # the option's kind.
@@ -909,7 +972,7 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         return None
 
     for i, tenant in enumerate(tenants):
-        for kind in TENANT_KINDS:
+        for kind in CO_KINDS:
             if not any(pair[i] == kind for pair in pairs):
                 continue
             run = run_pair(card, [{"mask": tenant["mask"], "kind": kind,

@@ -30,7 +30,9 @@ FP8 or block-scaled MX instructions in place of the bf16 one, and
 bf16 GEMM whose operands travel global memory -> LDS -> MFMA;
 --co-tenancy-gemm-form runs that GEMM block-scaled, MXFP8 or MXFP4, and
 --co-tenancy-gemm-loads direct the bf16 one with its slabs loaded straight
-from memory into LDS.
+from memory into LDS. --co-tenancy-decode runs the decode shape of the
+block-scaled GEMM, 32 token rows against a weight matrix streamed from
+memory, beside itself, the streamer and the prefill GEMM.
 """
 from __future__ import annotations
 
@@ -84,6 +86,17 @@ def gemm_forms_arg(text: str):
 
     forms = tuple(text.split(","))
     if not all("gemm-" + f in MXGEMM_KINDS for f in forms):
+        raise argparse.ArgumentTypeError(
+            f"expected forms out of mxfp8, mxfp4 as FORM[,FORM...], got {text!r}")
+    return forms
+
+
+def decode_forms_arg(text: str):
+    """"FORM[,FORM...]": forms of the decode tenant."""
+    from elastic_gpu_scheduler_amd.agent.cotenancy import DECODE_KINDS
+
+    forms = tuple(text.split(","))
+    if not all("decode-" + f in DECODE_KINDS for f in forms):
         raise argparse.ArgumentTypeError(
             f"expected forms out of mxfp8, mxfp4 as FORM[,FORM...], got {text!r}")
     return forms
@@ -191,6 +204,20 @@ def build_parser() -> argparse.ArgumentParser:
                         "GEMMs on gfx950 do; not together with "
                         "--co-tenancy-gemm-form, whose kinds have no such "
                         "path")
+    p.add_argument("--co-tenancy-decode", nargs="?", type=decode_forms_arg,
+                   const=("mxfp4",), default=None, metavar="FORM[,FORM]",
+                   help="with --co-tenancy: instead of the FMA and stream "
+                        "pairs, run a tenant in the decode shape of a "
+                        "block-scaled GEMM, 32 token rows against 1 GiB of "
+                        "weights streamed from memory, out of mxfp4 (the "
+                        "default) and mxfp8: the kinds decode-mxfp4 and "
+                        "decode-mxfp8, next to another such tenant, next to "
+                        "the 1 GiB streamer and next to the prefill bf16 GEMM "
+                        "(both ways round each); one report per card and "
+                        "form, each ratio split into clock_ratio and "
+                        "cycle_ratio; not together with --co-tenancy-cache, "
+                        "--co-tenancy-chase, --co-tenancy-mfma or "
+                        "--co-tenancy-gemm")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -230,7 +257,10 @@ def main(argv=None) -> int:
              ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma")),
             ("--co-tenancy-gemm-form", "--co-tenancy-gemm", ()),
             ("--co-tenancy-gemm-loads", "--co-tenancy-gemm",
-             ("--co-tenancy-gemm-form",))):
+             ("--co-tenancy-gemm-form",)),
+            ("--co-tenancy-decode", "--co-tenancy",
+             ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma",
+              "--co-tenancy-gemm"))):
         if not given(flag):
             continue
         if not given(needs):
@@ -243,12 +273,16 @@ def main(argv=None) -> int:
 
     if args.co_tenancy is not None:
         from elastic_gpu_scheduler_amd.agent.cotenancy import (
-            CACHE_PAIRS, CHASE_PAIRS, GEMM_PAIRS, MFMA_PAIRS, cache_passes, mxgemm_pairs)
+            CACHE_PAIRS, CHASE_PAIRS, GEMM_PAIRS, MFMA_PAIRS, cache_passes, decode_pairs,
+            mxgemm_pairs)
 
         # What every report of the run is asked for and, where a flag names
         # several forms or sizes, what each of them adds, by its label.
         common, each = {}, None
-        if args.co_tenancy_gemm_form is not None:
+        if args.co_tenancy_decode is not None:
+            each = {form: {"pairs": decode_pairs("decode-" + form)}
+                    for form in args.co_tenancy_decode}
+        elif args.co_tenancy_gemm_form is not None:
             each = {form: {"pairs": mxgemm_pairs("gemm-" + form)}
                     for form in args.co_tenancy_gemm_form}
         elif args.co_tenancy_gemm:

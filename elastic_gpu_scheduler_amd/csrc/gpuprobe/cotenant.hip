@@ -8,7 +8,9 @@
 //     MFMAs (bf16, or the fp8, mxfp8 or mxfp4 form) issued back to back on
 //     operands held in registers or re-read from LDS every step ("mfma"),
 //     or a whole GEMM fed from memory through LDS, bf16 ("gemm") or
-//     block-scaled ("gemm-mxfp8", "gemm-mxfp4"),
+//     block-scaled ("gemm-mxfp8", "gemm-mxfp4"), or the decode shape of the
+//     latter, 32 rows against weights streamed from memory straight into
+//     registers ("decode-mxfp8", "decode-mxfp4"),
 //     each launch stamped with the device's constant-rate wall clock. The
 //     clock is the card's, not the
 //     process's, so two separate processes can lay their launches side by
@@ -1683,10 +1685,400 @@ tenant_gemm_direct_kernel(const int4v* __restrict__ a, const int4v* __restrict__
 }
 #pragma clang diagnostic pop
 
+// ---- decode-mxfp8, decode-mxfp4 ----------------------------------------------
+
+constexpr int kDecodeRows = 32;       // rows of A: the tokens of one decode step
+constexpr int kDecodeDefaultK = 8192;
+constexpr uint64_t kDecodeMaxN = 1 << 20;
+// A default launch lasts about as long as the gemm kinds' default launches
+// (profiles/decode_cotenancy_results.md).
+constexpr int kDecodeDefaultPasses[kMfmaForms] = {0, 0, 48, 48};
+// Steps of loads a wave keeps in flight, and the workgroups per CU (waves per
+// SIMD) the kernel is built for at least: 2 and 5, measured against 3 steps
+// at 4 waves, 4 at 3 and 8 at 2 (profiles/decode_cotenancy_results.md: all
+// four within 1 % of each other for mxfp8, the kept one ahead; for mxfp4
+// eight steps at two waves 1.5 % ahead of the other three).
+#ifndef GPUPROBE_DECODE_DISTANCE
+#define GPUPROBE_DECODE_DISTANCE 2
+#endif
+#ifndef GPUPROBE_DECODE_WAVES
+#define GPUPROBE_DECODE_WAVES 5
+#endif
+constexpr int kDecodeDistance = GPUPROBE_DECODE_DISTANCE;
+constexpr int kDecodeWaves = GPUPROBE_DECODE_WAVES;
+// A distance of 1 is not built: its mxfp4 launch under a half-card mask did
+// not end within two minutes on the card, cause not found
+// (profiles/decode_cotenancy_results.md).
+static_assert(kDecodeDistance >= 2 && kDecodeDistance <= 8, "register sets of a wave");
+static_assert(kDecodeWaves >= 1 && kDecodeWaves <= 8, "waves per SIMD");
+
+// Which 16-byte chunk (0..7) of a row's 128-byte step lane half h holds in
+// piece p (0..3) of its registers; see the kernel.
+template <int F>
+__device__ constexpr uint32_t decode_chunk(uint32_t p, uint32_t h) {
+  return F == kMxfp8 ? 2 * p + h : 4 * h + p;
+}
+
+// The operands of a decode tenant. `buf` is A (32 x K, row-major) followed by
+// W (N x K, row n holding column n of the product's right-hand side), the
+// elements of tenant_mxgemm_fill_kernel's A and B: one 16-byte store of 16 or
+// 32 elements per step, grid-stride, v16 = 8 x steps the stores of a row and
+// n16 = (32 + N) v16 those of both matrices. `scales` is step-major as there:
+// A's words [steps][32], then W's [steps][N], byte b of a word the scale of
+// the step's block b; nwords = (32 + N) x steps. All indices are 64-bit,
+// below n16 and below nwords. (A kernel of its own, so that the fill the
+// gemm kinds were measured with stays as it is.)
+template <int F>
+__global__ void __launch_bounds__(kBlock)
+tenant_decode_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint64_t v16,
+                          typename MxGemm<F>::Word* __restrict__ scales, uint64_t nwords,
+                          uint64_t n, uint32_t key) {
+  using G = MxGemm<F>;
+  constexpr uint32_t kPerDword = F == kMxfp8 ? 4 : 8;  // elements of one dword
+  const uint64_t first = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+  for (uint64_t i = first; i < n16; i += stride) {
+    const uint64_t line = i / v16;
+    const bool is_w = line >= kDecodeRows;
+    const uint32_t row = static_cast<uint32_t>((is_w ? line - kDecodeRows : line) % kGemmRowPeriod);
+    const uint32_t k0 = static_cast<uint32_t>((i % v16) * (4 * kPerDword) % kGemmKPeriod);
+    int4v v;
+#pragma unroll
+    for (uint32_t d = 0; d < 4; ++d) {
+      uint32_t word = 0;
+#pragma unroll
+      for (uint32_t q = 0; q < kPerDword; ++q) {
+        const uint32_t k = k0 + kPerDword * d + q;
+        const uint32_t hash = is_w ? mfma_b_hash<F>(key, k, row) : mfma_a_hash<F>(key, row, k);
+        if constexpr (F == kMxfp8)
+          word |= to_e4m3_bits(static_cast<int>(hash % 15u) - 7) << (8 * q);
+        else
+          word |= (hash & 15u) << (4 * q);
+      }
+      v[d] = static_cast<int>(word);
+    }
+    buf[i] = v;
+  }
+  const uint64_t a_words = nwords / (kDecodeRows + n) * kDecodeRows;  // steps x 32
+  for (uint64_t i = first; i < nwords; i += stride) {
+    const bool is_w = i >= a_words;
+    const uint64_t rows = is_w ? n : kDecodeRows, at = is_w ? i - a_words : i;
+    const uint32_t row = static_cast<uint32_t>((at % rows) % kGemmRowPeriod);
+    const uint32_t blk0 = static_cast<uint32_t>((at / rows) * G::kWordBytes % 3);
+    uint32_t word[2] = {0, 0};
+#pragma unroll
+    for (uint32_t b = 0; b < G::kWordBytes; ++b) {
+      const uint32_t blk = (blk0 + b) % 3;
+      uint32_t byte;
+      if constexpr (F == kMxfp8)
+        byte = 127u + (is_w ? mfma_b_scale_bit<F>(key, blk, row)
+                            : mfma_a_scale_bit<F>(key, row, blk));
+      else
+        byte = 128u + (is_w ? 0u : mfma_a_scale_bit<F>(key, row, blk));
+      word[b / 4] |= byte << (8 * (b % 4));
+    }
+    if constexpr (F == kMxfp8)
+      scales[i] = static_cast<int>(word[0]);
+    else
+      scales[i] = int2v{static_cast<int>(word[0]), static_cast<int>(word[1])};
+  }
+}
+
+// One step's loads of a lane, as they come from global memory: the scale
+// words of its weight row and of its row of A, its chunk of A's slab and the
+// four pieces of its weight row.
+template <int F>
+struct DecodeFetch {
+  typename MxGemm<F>::Word sw, sa;
+  int4v a, w[4];
+};
+
+// Sub-step S of a decode step: acc += A x W^T over 64 k, one MFMA. `a` and
+// `w` are the lane's four pieces of the step, `sa` and `sw` its scale
+// registers for the sub-step, the byte picked by op_sel `kSel` (mx_step's 0
+// and 2, the two values every checksum on the card was exact with).
+template <int F, int S, int kSel>
+__device__ inline f32x16 decode_mfma(const int4v (&a)[4], const int4v (&w)[4], f32x16 acc,
+                                     int sa, int sw) {
+  if constexpr (F == kMxfp8) {
+    const int4v al = a[2 * S], ah = a[2 * S + 1], wl = w[2 * S], wh = w[2 * S + 1];
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+        int8v{al[0], al[1], al[2], al[3], ah[0], ah[1], ah[2], ah[3]},
+        int8v{wl[0], wl[1], wl[2], wl[3], wh[0], wh[1], wh[2], wh[3]}, acc, 0, 0, kSel, sa, kSel,
+        sw);
+  } else {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+        MfmaFrags<F>::widen(a[S]), MfmaFrags<F>::widen(w[S]), acc, 4, 4, kSel, sa, kSel, sw);
+  }
+}
+
+// The decode shape of a block-scaled GEMM: a few token rows against a weight
+// matrix that is read once, C (32 x N, f32 accumulators, never stored) = A
+// (32 x K) . W^T, W stored N x K, MXFP8 or MXFP4 under E8M0 scales per block
+// of 32 k, K = 128 (mxfp8) or 256 (mxfp4) x steps, N = 128 x tiles. Every
+// byte of W is used for 32 rows of C and never again, so the kernel streams
+// W from memory at about 64 (mxfp8) or 128 (mxfp4) flop per byte and HBM,
+// not the MFMA pipe, sets its pace. The grid is tiles x passes workgroups;
+// workgroup g computes tile g % tiles of pass g / tiles, every pass the same
+// product and a whole re-read of W.
+//
+// Work split. A workgroup owns 128 rows of W (128 columns of C) over the
+// whole K; wave j owns rows 32 j .. 32 j + 31 and one 32 x 32 accumulator,
+// output register reg row (reg & 3) + 8 (reg >> 2) + 4 h of column r as in
+// every kernel here. A is the MFMA's first operand and W its second. A step
+// is 128 bytes of every row, two (mxfp8) or four (mxfp4) sub-steps of one
+// v_mfma_scale_f32_32x32x64_f8f6f4: per wave and step 4 KiB of W and 128
+// cycles of MFMA.
+//
+// Which k a lane holds (decode_chunk). The step's 128 bytes are eight 16-byte
+// chunks, and a lane keeps four of them, pieces p = 0..3, of its row. Any
+// assignment is correct that A's fragments and both scale selections share.
+//   mxfp4: a chunk is a block of 32 k and sub-step s multiplies piece s.
+//     Lane half h holds chunks 4 h + s: the 64 contiguous bytes 64 h .. 64 h
+//     + 63 of its row's step, four buffer_load_dwordx4 at consecutive
+//     immediate offsets (the prefill kernels' 2 s + h gave a lane four pieces
+//     32 bytes apart). One load instruction touches 16 bytes at 64 h + 16 s of
+//     each of the wave's 32 rows, and the four of a step together every byte
+//     of 32 lines of 128 bytes.
+//   mxfp8: a block is two chunks, and the instruction scales a lane's low
+//     four dwords by the scale register of lane r and its high four by that
+//     of lane r + 32 (MfmaFrags), so the low dwords of lanes r and r + 32
+//     have to be the two halves of one block and a lane cannot hold 32
+//     contiguous bytes. Sub-step s multiplies pieces 2 s (low) and 2 s + 1
+//     (high); piece p of lane half h is chunk 2 p + h, half h of block p.
+//     One load instruction touches the 32 contiguous bytes of block p of
+//     each of the 32 rows.
+//
+// Weights: global memory -> registers, in fragment layout, no LDS and no
+// ds_write, because no other wave ever needs them. Buffer loads on a
+// descriptor of exactly the tile's 128 rows (at most 128 x 32768 bytes); the
+// lane's offset is (32 j + r) x row bytes + 16 x chunk(0, h), the piece an
+// immediate, the step (128 x step) the shared offset.
+//
+// Scales: global memory -> registers as in tenant_mxgemm_kernel, one word per
+// lane, step and operand (lanes r and r + 32 the same one), step-major so
+// that a wave's 32 rows are 128 or 256 contiguous bytes. The lane supplies
+// the scale of its own half's block: mxfp8 block 2 s + h, byte 2 s of the word
+// shifted right by 8 h, op_sel 2 s; mxfp4 block 4 h + s, byte s of dword h,
+// which sub-steps 0 and 2 pick with op_sel 0 and 2 and sub-steps 1 and 3 with
+// the same two from the dword shifted right by 8: one or two shifts per step
+// and operand, and no op_sel value the card has not been seen exact with.
+//
+// Activations: global memory -> registers -> LDS, shared by the four waves.
+// A step's slab of A is 32 rows x 128 bytes, 4 KiB: one 16-byte load and one
+// ds_write_b128 per lane. LDS holds it in fragment order, plane p = the 64
+// lanes' piece p at 16 x lane: wave p loads and writes plane p (lane r + 32 h
+// fetches chunk(p, h) of row r), and every wave reads its four pieces as
+// plane base + 16 x lane. Writes and reads alike are 64 lanes on 1 KiB of
+// consecutive addresses, so neither has a bank conflict and nothing is
+// swizzled. Two buffers of 4 KiB and 2 KiB for the reduction: 10 KiB. A is
+// not kept resident: at the forms' largest K it is 1 MiB (mxfp8) or 256 KiB
+// (mxfp4). It is re-read by every workgroup, 32 rows against the tile's 128,
+// and is served by the L2 after its first use.
+//
+// Pipeline: D = kDecodeDistance steps in flight per wave. A step is only 4
+// KiB per wave and 128 cycles of MFMA, and a dependent load from HBM takes
+// about 900 cycles on an idle card (profiles/chase_cotenancy_results.md), so
+// one step ahead covers nothing. Register set u = i % D holds the loads of
+// step i: seven loads, always in the order slab chunk, W's scale word, A's
+// scale word, weight pieces 0..3. Step i reads A's fragments from LDS buffer
+// i & 1, takes its scales, issues the first three loads of step i + D into
+// the same set, then its MFMAs, each followed by the loads that replace the
+// pieces it has just read; it writes the slab of step i + 1 (set (u + 1) % D,
+// loaded D - 1 steps ago) to buffer (i + 1) & 1 and crosses one barrier.
+// Scheduling barriers (pin) keep the compiler from moving a load or the
+// next step's scale selection, so prologue and steps issue in one order.
+// That buffer
+// was last read in step i - 1, which every wave left through the barrier
+// before. The loop is unrolled D times so that every set is a fixed one, and
+// runs ceil(steps / D) x D steps: a step past the last loads nothing (every
+// lane's offset is moved outside the descriptors, kBufferOutside, which the
+// hardware answers with zeros without reading memory), so its elements and
+// scale bytes are zero, its products are +0 and the accumulators stay as
+// they are. Hence no load and no barrier has a branch around it but the
+// loop's own, every step issues the same seven loads in the same order, and
+// every counted vmcnt the compiler places means the same in every step. In
+// the gfx950 assembly of D = 2 every step waits vmcnt(11) for its scale
+// words, vmcnt(12) (mxfp8) or vmcnt(13) (mxfp4) in front of each MFMA and
+// vmcnt(13) in front of the slab write: each leaves the whole newer set
+// outstanding, and the loop holds no vmcnt(0); at D = 4 the counts are 25,
+// 26 or 27 and 27. With D x 4 KiB per wave and 4 x 5 waves a CU has 160 KiB
+// of W in flight at D = 2; the same bytes in flight as fewer, deeper waves
+// (D = 3 at four waves, 4 at three, 8 at two) measured within 1.5 %.
+//
+// The tile walk is the plain one, tile g % tiles: no byte of W is read by two
+// workgroups of a pass, so there is nothing for gemm_order to keep in an L2,
+// and A is in every L2. A tile's rows are one contiguous piece of memory.
+//
+// Bounds. N and K are multiples of the tile and of the step. W: (32 j + r) x
+// row bytes + 16 x chunk + 128 x step + 15 with 32 j + r < 128, chunk < 8 and
+// step < steps is below 128 x row bytes, the window. A: the same with r < 32
+// in a window of 32 rows. W's scale words: window from the tile's first word
+// to its last of the last step, ((steps - 1) N + 128) words, offset step x N +
+// 32 j + r; A's: steps x 32 words, offset 32 step + r. Every window is below
+// 2^31 bytes (W's scale words of all tiles at most 2^20 x 256 x 4). An LDS
+// index is buffer x 256 + 64 p + lane < 512.
+//
+// Exactness. The elements and scales are the prefill kernels', so their
+// bounds hold: K <= 32768 (mxfp8) and 16384 (mxfp4) keep every accumulator
+// an exact integer in f32.
+//
+// Result. Every lane weighs its 16 entries at (m, n), n global, by (1 + m) (1
+// + n) modulo 2^64; the 256 sums are added up through LDS and thread 0
+// stores the workgroup's word (gemm_store_sum). Stamps and clocks are
+// clocked_end's. No FP32 arithmetic but the MFMAs' is written here.
+//
+// hipcc -O3 for gfx950 reports (-Rpass-analysis=kernel-resource-usage), mxfp8
+// and mxfp4: 89 and 94 VGPRs (16 of accumulator, 2 x 22 or 24 of loads in
+// flight, 16 of A's fragments), no AGPRs, 45 and 49 SGPRs, no scratch and no
+// spills, 10240 bytes of LDS and an occupancy of 5 waves per SIMD, by
+// registers. Every kernel that was here before reports what it did.
+//
+// On the card (profiles/decode_cotenancy_results.md) the default window
+// streams its weights at 5.2 (mxfp8) and 4.6 TB/s (mxfp4) where the stream
+// tenant reads 6.5-6.8, at an unlowered clock of 2.39 GHz, and on half the
+// CUs at 0.56 of that where the streamer keeps 6.1; neither the distance nor
+// the waves move it. So the limit is in the CUs, not HBM; a load instruction
+// touches 32 lines of 128 bytes, one per row, for 1 KiB, but which unit it
+// is was not measured.
+template <int F>
+__global__ void __launch_bounds__(kBlock, kDecodeWaves)
+tenant_decode_kernel(const int4v* __restrict__ a, const int4v* __restrict__ w,
+                     const typename MxGemm<F>::Word* __restrict__ sa,
+                     const typename MxGemm<F>::Word* __restrict__ sw, uint32_t tiles,
+                     uint32_t steps, unsigned long long* __restrict__ out,
+                     unsigned long long* __restrict__ rec,
+                     unsigned long long* __restrict__ clk) {
+  using G = MxGemm<F>;
+  constexpr int D = kDecodeDistance;
+  constexpr uint32_t kPiece = 16 * (decode_chunk<F>(1, 0) - decode_chunk<F>(0, 0));
+  __shared__ int4v slab[2][kBlock];  // [buffer][plane x 64 + lane]
+  __shared__ unsigned long long sums[kBlock];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = lane & 31u, h = lane >> 5;
+  const uint32_t wave = threadIdx.x / 64;
+  const uint32_t tile = blockIdx.x % tiles;
+  const uint32_t n_rows = tiles * kGemmTile;
+  const uint32_t row_bytes = steps * (kGemmRowVecs * 16);
+  const uint32_t w_at = (32 * wave + r) * row_bytes + 16 * decode_chunk<F>(0, h);
+  const uint32_t a_at = r * row_bytes + 16 * decode_chunk<F>(wave, h);
+  const uint32_t sw_at = (32 * wave + r) * G::kWordBytes, sa_at = r * G::kWordBytes;
+  const auto window = [](const auto* first, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(first)),
+                                             0, static_cast<int>(bytes), kBufferWord3);
+  };
+  const auto rw = window(w + static_cast<uint64_t>(tile) * kGemmTile * (row_bytes / 16),
+                         kGemmTile * row_bytes);
+  const auto ra = window(a, kDecodeRows * row_bytes);
+  const auto rsw = window(sw + tile * kGemmTile,
+                          ((steps - 1) * n_rows + kGemmTile) * G::kWordBytes);
+  const auto rsa = window(sa, steps * kDecodeRows * G::kWordBytes);
+
+  DecodeFetch<F> p[D];
+  // Nothing is scheduled across a pin: the loads keep the order they are
+  // written in, the same in the prologue and in every step.
+  const auto pin = [] { __builtin_amdgcn_sched_barrier(0); };
+  // The loads of step `at_step`, past the last step outside every window:
+  // first the slab chunk and the two scale words, then the weight pieces.
+  const auto fetch_head = [&](DecodeFetch<F>& f, uint32_t at_step)
+      __attribute__((always_inline)) {
+    const uint32_t outside = at_step < steps ? 0u : kBufferOutside;
+    f.a = __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(
+        ra, a_at | outside, at_step * (kGemmRowVecs * 16), 0));
+    pin();
+    f.sw = mx_load_word<F>(rsw, sw_at | outside, at_step * n_rows * G::kWordBytes);
+    pin();
+    f.sa = mx_load_word<F>(rsa, sa_at | outside, at_step * kDecodeRows * G::kWordBytes);
+    pin();
+  };
+  const auto fetch_piece = [&](DecodeFetch<F>& f, uint32_t at_step, uint32_t pc)
+      __attribute__((always_inline)) {
+    const uint32_t outside = at_step < steps ? 0u : kBufferOutside;
+    f.w[pc] = __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(
+        rw, (w_at | outside) + kPiece * pc, at_step * (kGemmRowVecs * 16), 0));
+    pin();
+  };
+  f32x16 acc;
+  // Step i from the set `mine`, which the loads of step i + D replace piece
+  // by piece behind the MFMA that read the piece; `next` holds the slab of
+  // step i + 1.
+  const auto step = [&](DecodeFetch<F>& mine, const DecodeFetch<F>& next, uint32_t i)
+      __attribute__((always_inline)) {
+    int4v af[4];
+#pragma unroll
+    for (int pc = 0; pc < 4; ++pc) af[pc] = slab[i & 1u][64 * pc + lane];
+    if constexpr (F == kMxfp8) {
+      const int ca = static_cast<int>(static_cast<uint32_t>(mine.sa) >> (8 * h));
+      const int cw = static_cast<int>(static_cast<uint32_t>(mine.sw) >> (8 * h));
+      pin();
+      fetch_head(mine, i + D);
+      acc = decode_mfma<F, 0, 0>(af, mine.w, acc, ca, cw);
+      pin();
+      fetch_piece(mine, i + D, 0);
+      fetch_piece(mine, i + D, 1);
+      acc = decode_mfma<F, 1, 2>(af, mine.w, acc, ca, cw);
+      pin();
+      fetch_piece(mine, i + D, 2);
+      fetch_piece(mine, i + D, 3);
+    } else {
+      const uint32_t ca = static_cast<uint32_t>(h ? mine.sa[1] : mine.sa[0]);
+      const uint32_t cw = static_cast<uint32_t>(h ? mine.sw[1] : mine.sw[0]);
+      const int ca1 = static_cast<int>(ca >> 8), cw1 = static_cast<int>(cw >> 8);
+      pin();
+      fetch_head(mine, i + D);
+      acc = decode_mfma<F, 0, 0>(af, mine.w, acc, static_cast<int>(ca), static_cast<int>(cw));
+      pin();
+      fetch_piece(mine, i + D, 0);
+      acc = decode_mfma<F, 1, 0>(af, mine.w, acc, ca1, cw1);
+      pin();
+      fetch_piece(mine, i + D, 1);
+      acc = decode_mfma<F, 2, 2>(af, mine.w, acc, static_cast<int>(ca), static_cast<int>(cw));
+      pin();
+      fetch_piece(mine, i + D, 2);
+      acc = decode_mfma<F, 3, 2>(af, mine.w, acc, ca1, cw1);
+      pin();
+      fetch_piece(mine, i + D, 3);
+    }
+    slab[(i + 1) & 1u][threadIdx.x] = next.a;
+    __syncthreads();
+    pin();
+  };
+
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  const unsigned long long t0 = stamp_start();
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) acc[reg] = 0.0f;
+  pin();
+#pragma unroll
+  for (int u = 0; u < D; ++u) {
+    fetch_head(p[u], u);
+#pragma unroll
+    for (uint32_t pc = 0; pc < 4; ++pc) fetch_piece(p[u], u, pc);
+  }
+  slab[0][threadIdx.x] = p[0].a;
+  __syncthreads();
+  pin();
+  for (uint32_t i = 0; i < steps; i += D) {
+#pragma unroll
+    for (int u = 0; u < D; ++u) step(p[u], p[(u + 1) % D], i + u);
+  }
+
+  uint64_t column = 0;
+#pragma unroll
+  for (uint32_t reg = 0; reg < 16; ++reg)
+    column += static_cast<uint64_t>(static_cast<int64_t>(static_cast<int>(acc[reg]))) *
+              static_cast<uint64_t>(1 + 4 * h + (reg & 3u) + 8 * (reg >> 2));
+  gemm_store_sum(sums, column * static_cast<uint64_t>(1 + tile * kGemmTile + 32 * wave + r), out);
+  clocked_end(rec, clk, c0, t0);
+}
+
 // ---- host ------------------------------------------------------------------
 
-enum class Kind : int { kFma, kStream, kCache, kChase, kMfma, kGemm, kGemmMxfp8, kGemmMxfp4 };
-constexpr int kKinds = 8;
+enum class Kind : int {
+  kFma, kStream, kCache, kChase, kMfma, kGemm, kGemmMxfp8, kGemmMxfp4, kDecodeMxfp8,
+  kDecodeMxfp4
+};
+constexpr int kKinds = 10;
 // Per kind: name, workgroups per CU (chase: one, that is one wave per SIMD;
 // the gemms: none, their grid is the problem's), whether it reads a buffer
 // filled beforehand, whether it takes form and operands.
@@ -1699,10 +2091,11 @@ constexpr KindInfo kKindTable[kKinds] = {
     {"fma", kGroupsPerCu, false, false},   {"stream", kGroupsPerCu, true, false},
     {"cache", kCacheGroupsPerCu, true, false}, {"chase", 1, true, false},
     {"mfma", kMfmaGroupsPerCu, false, true},   {"gemm", 0, true, false},
-    {"gemm-mxfp8", 0, true, false},            {"gemm-mxfp4", 0, true, false}};
+    {"gemm-mxfp8", 0, true, false},            {"gemm-mxfp4", 0, true, false},
+    {"decode-mxfp8", 0, true, false},          {"decode-mxfp4", 0, true, false}};
 
-// Whether a kind is one of the three GEMMs, and whether a block-scaled one;
-// the form of the latter is the kind's.
+// Whether a kind is one of the GEMMs, the decode-shaped ones included, and
+// whether a block-scaled one; the form of the latter is the kind's.
 constexpr bool is_gemm(Kind k) { return k >= Kind::kGemm; }
 constexpr bool is_mxgemm(Kind k) { return k > Kind::kGemm; }
 
@@ -1757,6 +2150,7 @@ struct TenantResult {
   int side = 0, tiles = 0;         // gemm only: tiles per side and per pass
   uint64_t m = 0, n = 0, k = 0;    // gemm only
   uint64_t scale_bytes = 0;        // block-scaled gemm only: A's and B's scale words
+  uint64_t lead_bytes = 0;         // decode only: A's elements, in the buffer before W's
   uint64_t load_bytes_per_launch = 0;  // gemm only
   // flops (fma, mfma, gemm), bytes (stream, cache) or hops (chase)
   double work_per_launch = 0.0;
@@ -1873,6 +2267,36 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
                                 (2 * kGemmSlabVecs * 16 + kWavesPerGroup * kGemmTile * word);
       break;
     }
+    case Kind::kDecodeMxfp8:
+    case Kind::kDecodeMxfp4: {
+      // agent/cotenancy.py states the same rule on its own (decode_shape). A
+      // row is 128 bytes a step in either form.
+      const bool f8 = kind == Kind::kDecodeMxfp8;
+      r.form = f8 ? kMxfp8 : kMxfp4;
+      const int step_k = f8 ? MxGemm<kMxfp8>::kStepK : MxGemm<kMxfp4>::kStepK;
+      const uint64_t word = f8 ? MxGemm<kMxfp8>::kWordBytes : MxGemm<kMxfp4>::kWordBytes;
+      if (iters <= 0) iters = kDecodeDefaultK / step_k;
+      r.iters = std::min(iters, f8 ? MxGemm<kMxfp8>::kMaxIters : MxGemm<kMxfp4>::kMaxIters);
+      r.k = static_cast<uint64_t>(step_k) * r.iters;
+      if (bytes == 0) bytes = kGiB;  // more than the Infinity Cache holds
+      const uint64_t n = bytes / (128ULL * r.iters) / kGemmTile * kGemmTile;
+      r.m = kDecodeRows;
+      r.n = std::min<uint64_t>(std::max<uint64_t>(n, kGemmTile), kDecodeMaxN);
+      r.bytes = 128 * r.n * r.iters;  // W's elements
+      r.lead_bytes = 128ULL * kDecodeRows * r.iters;
+      r.scale_bytes = (kDecodeRows + r.n) * r.iters * word;
+      r.tiles = static_cast<int>(r.n / kGemmTile);
+      if (passes <= 0) passes = kDecodeDefaultPasses[r.form];
+      r.passes = std::min(passes, kGemmMaxGroups / r.tiles);
+      r.workgroups = r.tiles * r.passes;
+      r.work_per_launch = 2.0 * r.m * r.n * r.k * r.passes;
+      // Per workgroup and step 16 KiB of W, the 4 KiB slab of A, and per wave
+      // the words of its 32 rows of W and of the 32 of A.
+      r.load_bytes_per_launch =
+          static_cast<uint64_t>(r.workgroups) * r.iters *
+          (kGemmTile * 128 + kDecodeRows * 128 + 2 * kWavesPerGroup * kDecodeRows * word);
+      break;
+    }
   }
   return r;
 }
@@ -1885,13 +2309,13 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
   // What a launch leaves: a word per lane, for gemm one per workgroup.
   const size_t lanes =
       static_cast<size_t>(r.workgroups) * (is_gemm(r.kind) ? 1 : kBlock);
-  const uint64_t n16 = r.bytes / 16;
+  const uint64_t n16 = (r.lead_bytes + r.bytes) / 16;
   DevBuf buf, scales, out;
   Mirror recs{r.recs}, clks{r.clks};
   // One record {~0, 0} per timed launch, and one more for the warm-up.
   recs.h.assign(2 * static_cast<size_t>(launches + 1), 0ULL);
   for (size_t i = 0; i < recs.h.size(); i += 2) recs.h[i] = ~0ULL;
-  if (kKindTable[static_cast<int>(r.kind)].reads) buf.alloc(r.bytes);
+  if (kKindTable[static_cast<int>(r.kind)].reads) buf.alloc(r.lead_bytes + r.bytes);
   if (is_mxgemm(r.kind)) scales.alloc(r.scale_bytes);
   switch (r.kind) {  // what a lane stores, and what else a launch records
     case Kind::kFma:
@@ -1901,6 +2325,8 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
     case Kind::kGemm:
     case Kind::kGemmMxfp8:
     case Kind::kGemmMxfp4:
+    case Kind::kDecodeMxfp8:
+    case Kind::kDecodeMxfp4:
       clks.h.assign(recs.h.size(), 0ULL);
       [[fallthrough]];
     default:
@@ -1926,6 +2352,13 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
       go(grid, kernel, buf.as<const int4v>(), buf.as<const int4v>() + n16 / 2, words,
          words + r.m * r.iters, static_cast<uint32_t>(r.side), static_cast<uint32_t>(r.iters),
          o64, rec, clk);
+    };
+    // A, then W behind it; A's scale words, then W's behind them.
+    const auto decode = [&](auto kernel, auto* words, unsigned long long* rec,
+                            unsigned long long* clk) {
+      go(grid, kernel, buf.as<const int4v>(), buf.as<const int4v>() + r.lead_bytes / 16, words,
+         words + kDecodeRows * r.iters, static_cast<uint32_t>(r.tiles),
+         static_cast<uint32_t>(r.iters), o64, rec, clk);
     };
     const auto launch = [&](int slot) {
       unsigned long long* rec = recs.at(2 * slot);
@@ -1959,7 +2392,20 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
           mxgemm(tenant_mxgemm_kernel<kMxfp4>, scales.as<const int2v>(), rec,
                  clks.at(2 * slot));
           break;
+        case Kind::kDecodeMxfp8:
+          decode(tenant_decode_kernel<kMxfp8>, scales.as<const int>(), rec, clks.at(2 * slot));
+          break;
+        case Kind::kDecodeMxfp4:
+          decode(tenant_decode_kernel<kMxfp4>, scales.as<const int2v>(), rec,
+                 clks.at(2 * slot));
+          break;
       }
+    };
+    // The fill of a decode tenant: A's and W's elements, then their scale words.
+    const auto decode_fill = [&](auto kernel, auto* words) {
+      go(dim3(kGroupsPerCu * cus), kernel, buf.as<int4v>(), n16,
+         static_cast<uint64_t>(r.iters) * kGemmRowVecs, words, (kDecodeRows + r.n) * r.iters,
+         r.n, mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
     };
     // The fill of a block-scaled gemm: elements, then A's and B's scale words.
     const auto mxfill = [&](auto kernel, auto* words) {
@@ -1985,6 +2431,12 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
         break;
       case Kind::kGemmMxfp4:
         mxfill(tenant_mxgemm_fill_kernel<kMxfp4>, scales.as<int2v>());
+        break;
+      case Kind::kDecodeMxfp8:
+        decode_fill(tenant_decode_fill_kernel<kMxfp8>, scales.as<int>());
+        break;
+      case Kind::kDecodeMxfp4:
+        decode_fill(tenant_decode_fill_kernel<kMxfp4>, scales.as<int2v>());
         break;
       default:
         break;
@@ -2045,6 +2497,8 @@ void summarise(TenantResult& r) {
     case Kind::kGemm:  // every workgroup's word weighted by its pass, from 1
     case Kind::kGemmMxfp8:
     case Kind::kGemmMxfp4:
+    case Kind::kDecodeMxfp8:
+    case Kind::kDecodeMxfp4:
       for (size_t g = 0; g < r.out.size(); ++g)
         r.checksum += (is_gemm(r.kind) ? 1 + g / r.tiles : g + 1) * r.out[g];
       for (size_t l = 0; l < r.launches.size(); ++l) {
@@ -2076,7 +2530,7 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     r.free_bytes = free_b;
-    if (free_b < r.bytes + r.scale_bytes + kGiB) {
+    if (free_b < r.lead_bytes + r.bytes + r.scale_bytes + kGiB) {
       r.skipped = true;
       return r;
     }
@@ -2105,7 +2559,8 @@ void register_cotenant(py::module_& m) {
         if (k == kKinds)
           throw py::value_error(
               "cu_tenant_run: kind must be \"fma\", \"stream\", \"cache\", "
-              "\"chase\", \"mfma\", \"gemm\", \"gemm-mxfp8\" or \"gemm-mxfp4\"");
+              "\"chase\", \"mfma\", \"gemm\", \"gemm-mxfp8\", \"gemm-mxfp4\", "
+              "\"decode-mxfp8\" or \"decode-mxfp4\"");
         int f = 0;
         while (f < kMfmaForms && form != kMfmaFormTable[f].name) ++f;
         if (f == kMfmaForms)
@@ -2185,6 +2640,8 @@ void register_cotenant(py::module_& m) {
           case Kind::kGemm:
           case Kind::kGemmMxfp8:
           case Kind::kGemmMxfp4:
+          case Kind::kDecodeMxfp8:
+          case Kind::kDecodeMxfp4:
             if (is_mxgemm(r.kind)) d["form"] = kMfmaFormTable[r.form].name;
             d["m"] = r.m;
             d["n"] = r.n;
@@ -2231,8 +2688,8 @@ void register_cotenant(py::module_& m) {
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
-      "\"cache\", \"chase\", \"mfma\", \"gemm\", \"gemm-mxfp8\" or \"gemm-mxfp4\", anything "
-      "else raises ValueError "
+      "\"cache\", \"chase\", \"mfma\", \"gemm\", \"gemm-mxfp8\", \"gemm-mxfp4\", "
+      "\"decode-mxfp8\" or \"decode-mxfp4\", anything else raises ValueError "
       "before the device is touched. After one untimed "
       "launch, `launches` (1..64) launches of the same work run back to back "
       "on one stream, each between its own pair of events; the grid is 32 x "
@@ -2466,6 +2923,42 @@ void register_cotenant(py::module_& m) {
       "iters * (32768 + 4 * 128 * 4 or 8), slabs plus every wave's scale "
       "words; the free-memory refusal counts bytes + scale_bytes; checksum "
       "equals gemm_checksum(..., form=).\n\n"
+      "decode-mxfp8, decode-mxfp4: the decode shape of that block-scaled GEMM, C "
+      "(32 x N, never stored) = A (32 x K) . W^T with W stored N x K and read "
+      "once per pass, so that HBM and not the matrix pipe sets the pace (64 "
+      "or 128 flop per byte of W). `iters` is the steps of 128 k (mxfp8; "
+      "clamped to 1 .. 256) or 256 k (mxfp4; 1 .. 64), 0: K = 8192; `bytes` is "
+      "W's elements, N = bytes // (128 iters) rounded down to a multiple of "
+      "128 and clamped to 128 .. 2^20 (0: 1 GiB, more than the Infinity Cache "
+      "holds), and the result reports the bytes really used, 128 N iters; "
+      "`passes` is the whole re-reads of W in one launch (default 48 for "
+      "both, a default launch lasting about as long as gemm's; clamped to 1 "
+      ".. 2^22 // tiles). Elements and scales are gemm-mxfp8's and "
+      "gemm-mxfp4's for A (rows 0 .. 31) and B (= W), written once before "
+      "anything is timed, and the K limits are theirs. The grid is tiles x "
+      "passes workgroups, tiles = N / 128, tile g % tiles in pass g // tiles, "
+      "in plain order. A workgroup owns 128 rows of W over the whole K, each "
+      "of its four waves 32 of them and one 32 x 32 accumulator; a step is "
+      "128 bytes of every row, 2 (mxfp8) or 4 (mxfp4) "
+      "v_mfma_scale_f32_32x32x64_f8f6f4 per wave. W goes from memory "
+      "straight to registers in fragment layout, buffer loads on a "
+      "descriptor of the tile's 128 rows, no LDS: an mxfp4 lane holds the 64 "
+      "contiguous bytes 64 h .. 64 h + 63 of its row's step (blocks 4 h + s "
+      "at sub-step s), an mxfp8 lane half h of each of the step's four "
+      "blocks (the instruction scales a lane's low and high dwords by the "
+      "scale registers of lanes r and r + 32). The 32 rows of A are shared by "
+      "the four waves through LDS, 4 KiB a step in fragment order, one load "
+      "and one ds_write_b128 per lane, two buffers and one barrier per step; "
+      "scale words go from memory to registers. Two steps of loads are in "
+      "flight per wave at five or six workgroups per CU; the loop runs whole "
+      "rounds of two steps, a step past the last loading nothing (outside "
+      "the buffers' range) and adding zeros. The result has the gemm kinds' "
+      "keys: form, m = 32, n, k, bytes (W's elements), scale_bytes = (32 + N) "
+      "iters x 4 or 8, passes, checksum = gemm_checksum(32, n, k, passes, "
+      "seed, form=), load_bytes_per_launch = tiles * passes * iters * (16384 "
+      "+ 4096 + 256 x 4 or 8), work_per_launch = 2 x 32 N K passes, rates in "
+      "GFLOP/s and the clocks. The free-memory refusal counts A, W and the "
+      "scale words. Neither takes a form, operands or loads.\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
