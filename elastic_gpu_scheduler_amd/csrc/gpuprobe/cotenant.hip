@@ -864,6 +864,66 @@ __device__ inline uint32_t gemm_slot(uint32_t row, uint32_t c) {
   return row * kGemmRowVecs + (c ^ gemm_key(row));
 }
 
+// One step's sixteen MFMAs of a wave on the slabs {A, B} of `from`. The lane
+// reads rows read_a / 8 and read_b / 8 (+ 32 t) of the slabs, chunk (2 s + h)
+// ^ read_key at sub-step s.
+__device__ inline void gemm_multiply(MfmaTile& acc, const int4v (*from)[kGemmSlabVecs],
+                                     uint32_t read_a, uint32_t read_b, uint32_t read_key,
+                                     uint32_t h) {
+  const auto read = [&](MfmaFrags<kBf16>& f, uint32_t s) {
+    const uint32_t c = (2 * s + h) ^ read_key;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f.a[t] = __builtin_bit_cast(bf16x8, from[0][read_a + 32 * kGemmRowVecs * t + c]);
+      f.b[t] = __builtin_bit_cast(bf16x8, from[1][read_b + 32 * kGemmRowVecs * t + c]);
+    }
+  };
+  MfmaFrags<kBf16> f[2];
+  read(f[0], 0);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (uint32_t s = 0; s < 4; ++s) {
+    if (s < 3) read(f[(s + 1) & 1u], s + 1);
+    mfma_step(f[s & 1u], acc);
+    if (s < 3) mfma_lds_interleave<4, 2>();
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// The lane's 64 accumulators as integers, the entry at (m, n), global, weighed
+// by (1 + m) (1 + n) modulo 2^64. The wave's tile starts at (row0 + 64 (wave
+// >> 1), col0 + 64 (wave & 1)).
+__device__ inline uint64_t gemm_tile_sum(const MfmaTile& acc, uint32_t row0, uint32_t col0,
+                                         uint32_t wave, uint32_t r, uint32_t h) {
+  uint64_t sum = 0;
+#pragma unroll
+  for (uint32_t t = 0; t < 4; ++t) {
+    const uint32_t m = row0 + 64 * (wave >> 1) + 32 * (t >> 1) + 4 * h;
+    const uint32_t n = col0 + 64 * (wave & 1u) + 32 * (t & 1u) + r;
+    uint64_t column = 0;
+#pragma unroll
+    for (uint32_t reg = 0; reg < 16; ++reg)
+      column += static_cast<uint64_t>(static_cast<int64_t>(
+                    static_cast<int>(acc[t >> 1][t & 1][reg]))) *
+                static_cast<uint64_t>(1 + m + (reg & 3u) + 8 * (reg >> 2));
+    sum += column * static_cast<uint64_t>(1 + n);
+  }
+  return sum;
+}
+
+// The 256 sums of a workgroup added up through LDS, its one word stored by
+// thread 0.
+__device__ inline void gemm_store_sum(unsigned long long* sums, uint64_t sum,
+                                      unsigned long long* __restrict__ out) {
+  sums[threadIdx.x] = sum;
+  __syncthreads();
+  for (uint32_t width = kBlock / 2; width > 0; width >>= 1) {
+    if (threadIdx.x < width) sums[threadIdx.x] += sums[threadIdx.x + width];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = sums[0];
+}
+
 // A bf16 GEMM whose operands travel global memory -> LDS -> MFMA: C (S x S,
 // f32 accumulators, never stored) = A (S x K) . B^T, B stored S x K, K =
 // 64 x steps, S = 128 x side. The grid is tiles x passes workgroups, tiles =
@@ -904,8 +964,8 @@ __device__ inline uint32_t gemm_slot(uint32_t row, uint32_t c) {
 // is enough: the buffer written in step i was last read in step i - 1, which
 // every wave left through the barrier before. Within a step the fragment
 // reads of sub-step s + 1 go in front of the first three MFMAs of sub-step s
-// (mfma_lds_interleave, two reads per 32 cycles of MFMA) into a second
-// register set; only sub-step 0's reads, which have to follow the barrier,
+// (gemm_multiply: mfma_lds_interleave, two reads per 32 cycles of MFMA) into
+// a second register set; only sub-step 0's reads, which have to follow the barrier,
 // are not covered by the wave's own MFMAs, and there the CU's other waves
 // issue theirs. The last step loads and writes nothing.
 //
@@ -921,7 +981,8 @@ __device__ inline uint32_t gemm_slot(uint32_t row, uint32_t c) {
 //
 // Result. Every lane converts its 64 accumulators to integers and weighs the
 // entry at (m, n), global, by (1 + m) (1 + n) modulo 2^64; the 256 sums are
-// added up through LDS and thread 0 stores the workgroup's one word out[g].
+// added up through LDS and thread 0 stores the workgroup's one word out[g]
+// (gemm_tile_sum, gemm_store_sum).
 // Stamps and clocks are the mfma kind's (clocked_end). The addresses of the
 // first slab are computed before the start stamp, its loads are inside it;
 // between the stamps nothing but the operand loads and that one store
@@ -930,7 +991,7 @@ __device__ inline uint32_t gemm_slot(uint32_t row, uint32_t c) {
 // No FP32 arithmetic but the MFMAs' is written here or in the fill, so the
 // compiler has nothing to pack into two-wide FP32 instructions.
 //
-// hipcc -O3 for gfx950 reports (-Rpass-analysis=kernel-resource-usage) 159
+// hipcc -O3 for gfx950 reports (-Rpass-analysis=kernel-resource-usage) 158
 // VGPRs, no AGPRs, 32 SGPRs, no scratch and no spills, 67584 bytes of LDS and
 // an occupancy of 2 waves per SIMD: two workgroups per CU by registers and
 // by LDS alike.
@@ -977,28 +1038,7 @@ tenant_gemm_kernel(const int4v* __restrict__ a, const int4v* __restrict__ b, uin
       to[1][write_at + 32 * kGemmRowVecs * i] = next[1][i];
     }
   };
-  const auto read = [&](MfmaFrags<kBf16>& f, const int4v (*from)[kGemmSlabVecs], uint32_t s) {
-    const uint32_t c = (2 * s + h) ^ read_key;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      f.a[t] = __builtin_bit_cast(bf16x8, from[0][read_a + 32 * kGemmRowVecs * t + c]);
-      f.b[t] = __builtin_bit_cast(bf16x8, from[1][read_b + 32 * kGemmRowVecs * t + c]);
-    }
-  };
   f32x16 acc[2][2];
-  // One step's sixteen MFMAs on the slabs of `from`.
-  const auto multiply = [&](const int4v (*from)[kGemmSlabVecs]) {
-    MfmaFrags<kBf16> f[2];
-    read(f[0], from, 0);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (uint32_t s = 0; s < 4; ++s) {
-      if (s < 3) read(f[(s + 1) & 1u], from, s + 1);
-      mfma_step(f[s & 1u], acc);
-      if (s < 3) mfma_lds_interleave<4, 2>();
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
 
   const unsigned long long c0 = __builtin_amdgcn_s_memtime();
   const unsigned long long t0 = stamp_start();
@@ -1008,73 +1048,18 @@ tenant_gemm_kernel(const int4v* __restrict__ a, const int4v* __restrict__ b, uin
   __syncthreads();
   for (uint32_t i = 0; i + 1 < steps; ++i) {
     fetch();  // step i + 1, in flight under the MFMAs of step i
-    multiply(slab[i & 1u]);
+    gemm_multiply(acc, slab[i & 1u], read_a, read_b, read_key, h);
     store(slab[(i + 1) & 1u]);
     __syncthreads();
   }
-  multiply(slab[(steps - 1) & 1u]);
-
-  uint64_t sum = 0;
-#pragma unroll
-  for (uint32_t t = 0; t < 4; ++t) {
-    const uint32_t m = row0 + 64 * (wave >> 1) + 32 * (t >> 1) + 4 * h;
-    const uint32_t n = col0 + 64 * (wave & 1u) + 32 * (t & 1u) + r;
-    uint64_t column = 0;
-#pragma unroll
-    for (uint32_t reg = 0; reg < 16; ++reg)
-      column += static_cast<uint64_t>(static_cast<int64_t>(
-                    static_cast<int>(acc[t >> 1][t & 1][reg]))) *
-                static_cast<uint64_t>(1 + m + (reg & 3u) + 8 * (reg >> 2));
-    sum += column * static_cast<uint64_t>(1 + n);
-  }
-  sums[threadIdx.x] = sum;
-  __syncthreads();
-  for (uint32_t width = kBlock / 2; width > 0; width >>= 1) {
-    if (threadIdx.x < width) sums[threadIdx.x] += sums[threadIdx.x + width];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = sums[0];
+  gemm_multiply(acc, slab[(steps - 1) & 1u], read_a, read_b, read_key, h);
+  gemm_store_sum(sums, gemm_tile_sum(acc, row0, col0, wave, r, h), out);
   clocked_end(rec, clk, c0, t0);
 }
 
 // ---- gemm-mxfp8, gemm-mxfp4 ------------------------------------------------
 
 using int2v = __attribute__((ext_vector_type(2))) int;
-
-// What tenant_gemm_kernel leaves, as functions. Part one: the lane's 64
-// accumulators as integers,
-// the entry at (m, n), global, weighed by (1 + m) (1 + n) modulo 2^64. The
-// wave's tile starts at (row0 + 64 (wave >> 1), col0 + 64 (wave & 1)).
-__device__ inline uint64_t gemm_tile_sum(const MfmaTile& acc, uint32_t row0, uint32_t col0,
-                                         uint32_t wave, uint32_t r, uint32_t h) {
-  uint64_t sum = 0;
-#pragma unroll
-  for (uint32_t t = 0; t < 4; ++t) {
-    const uint32_t m = row0 + 64 * (wave >> 1) + 32 * (t >> 1) + 4 * h;
-    const uint32_t n = col0 + 64 * (wave & 1u) + 32 * (t & 1u) + r;
-    uint64_t column = 0;
-#pragma unroll
-    for (uint32_t reg = 0; reg < 16; ++reg)
-      column += static_cast<uint64_t>(static_cast<int64_t>(
-                    static_cast<int>(acc[t >> 1][t & 1][reg]))) *
-                static_cast<uint64_t>(1 + m + (reg & 3u) + 8 * (reg >> 2));
-    sum += column * static_cast<uint64_t>(1 + n);
-  }
-  return sum;
-}
-
-// Part two: the 256 sums added up through LDS, the workgroup's one word
-// stored by thread 0.
-__device__ inline void gemm_store_sum(unsigned long long* sums, uint64_t sum,
-                                      unsigned long long* __restrict__ out) {
-  sums[threadIdx.x] = sum;
-  __syncthreads();
-  for (uint32_t width = kBlock / 2; width > 0; width >>= 1) {
-    if (threadIdx.x < width) sums[threadIdx.x] += sums[threadIdx.x + width];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = sums[0];
-}
 
 // What the two block-scaled GEMMs differ in. A slab row is 128 bytes in
 // either form, as in the bf16 kernel: 128 k of e4m3 or 256 k of e2m1, that is
@@ -1104,35 +1089,37 @@ struct MxGemm {
 constexpr int kMxGemmDefaultSide = 8192;
 constexpr int kMxGemmDefaultPasses[kMfmaForms] = {0, 0, 32, 64};
 
-// The operands of a block-scaled gemm tenant. `buf` is A (S x K, row-major)
-// followed by B (S x K, row n holding column n), e4m3 bytes or e2m1 nibbles,
-// low nibble first: element (row, k) is that of MfmaFrags<F> at mfma_a_hash<F>
-// (key, row % 192, k % 96) or mfma_b_hash<F>(key, k % 96, row % 192), mxfp8
-// hash % 15 - 7 and mxfp4 the code hash & 15. One 16-byte store of 16 or 32
-// elements per step, grid-stride; v16 = 8 x steps counts the stores of a row
-// and n16 = 2 S v16 those of both matrices. 96 is a multiple of 16 and of 32,
-// so a store never straddles the k period.
+// The operands of a block-scaled gemm or decode tenant. `buf` is A (rows_a x
+// K, row-major) followed by B (rows_b x K, row n holding column n), S and S
+// rows for the gemm kinds, 32 and N for decode (whose B is W); e4m3 bytes or
+// e2m1 nibbles, low nibble first: element (row, k) is that of MfmaFrags<F> at
+// mfma_a_hash<F>(key, row % 192, k % 96) or mfma_b_hash<F>(key, k % 96, row %
+// 192), mxfp8 hash % 15 - 7 and mxfp4 the code hash & 15. One 16-byte store of
+// 16 or 32 elements per step, grid-stride; v16 = 8 x steps counts the stores
+// of a row and n16 = (rows_a + rows_b) v16 those of both matrices. 96 is a
+// multiple of 16 and of 32, so a store never straddles the k period.
 //
-// `scales` is step-major: A's words [steps][S], then B's [steps][S], one word
-// per row and step, byte b the scale of the step's block b, that is of block
-// ((k % 96) / 32) of the hashes with k = kStepK x step + 32 b: mxfp8 127 + e
-// on both sides, mxfp4 128 + e for A and 128 for B, e the form's scale bit.
-// So the 32 rows of a fragment are 128 or 256 contiguous bytes. nwords = 2 x
-// steps x S. All indices are 64-bit, below n16 and below nwords.
+// `scales` is step-major: A's words [steps][rows_a], then B's [steps][rows_b],
+// one word per row and step, byte b the scale of the step's block b, that is
+// of block ((k % 96) / 32) of the hashes with k = kStepK x step + 32 b: mxfp8
+// 127 + e on both sides, mxfp4 128 + e for A and 128 for B, e the form's scale
+// bit. So the 32 rows of a fragment are 128 or 256 contiguous bytes. nwords =
+// (rows_a + rows_b) x steps. All indices are 64-bit, below n16 and below
+// nwords.
 template <int F>
 __global__ void __launch_bounds__(kBlock)
 tenant_mxgemm_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint64_t v16,
                           typename MxGemm<F>::Word* __restrict__ scales, uint64_t nwords,
-                          uint64_t s, uint32_t key) {
+                          uint64_t rows_a, uint64_t rows_b, uint32_t key) {
   using G = MxGemm<F>;
   constexpr uint32_t kPerDword = F == kMxfp8 ? 4 : 8;  // elements of one dword
   const uint64_t first = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
   for (uint64_t i = first; i < n16; i += stride) {
-    const bool is_b = i >= n16 / 2;
-    const uint64_t at = is_b ? i - n16 / 2 : i;
-    const uint32_t row = static_cast<uint32_t>((at / v16) % kGemmRowPeriod);
-    const uint32_t k0 = static_cast<uint32_t>((at % v16) * (4 * kPerDword) % kGemmKPeriod);
+    const uint64_t line = i / v16;
+    const bool is_b = line >= rows_a;
+    const uint32_t row = static_cast<uint32_t>((is_b ? line - rows_a : line) % kGemmRowPeriod);
+    const uint32_t k0 = static_cast<uint32_t>((i % v16) * (4 * kPerDword) % kGemmKPeriod);
     int4v v;
 #pragma unroll
     for (uint32_t d = 0; d < 4; ++d) {
@@ -1150,11 +1137,12 @@ tenant_mxgemm_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint64_t v16,
     }
     buf[i] = v;
   }
+  const uint64_t a_words = nwords / (rows_a + rows_b) * rows_a;  // steps x rows_a
   for (uint64_t i = first; i < nwords; i += stride) {
-    const bool is_b = i >= nwords / 2;
-    const uint64_t at = is_b ? i - nwords / 2 : i;
-    const uint32_t row = static_cast<uint32_t>((at % s) % kGemmRowPeriod);
-    const uint32_t blk0 = static_cast<uint32_t>((at / s) * G::kWordBytes % 3);
+    const bool is_b = i >= a_words;
+    const uint64_t rows = is_b ? rows_b : rows_a, at = is_b ? i - a_words : i;
+    const uint32_t row = static_cast<uint32_t>((at % rows) % kGemmRowPeriod);
+    const uint32_t blk0 = static_cast<uint32_t>((at / rows) * G::kWordBytes % 3);
     uint32_t word[2] = {0, 0};
 #pragma unroll
     for (uint32_t b = 0; b < G::kWordBytes; ++b) {
@@ -1181,6 +1169,12 @@ tenant_mxgemm_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint64_t v16,
 // offset into its range check.
 constexpr int kBufferWord3 = 0x00020000;
 constexpr uint32_t kBufferOutside = 0x80000000u;
+
+// The descriptor of the `bytes` bytes that start at `first`.
+__device__ inline __amdgpu_buffer_rsrc_t buffer_window(const void* first, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(first), 0, static_cast<int>(bytes),
+                                           kBufferWord3);
+}
 
 template <int F>
 __device__ inline typename MxGemm<F>::Word mx_load_word(__amdgpu_buffer_rsrc_t window,
@@ -1372,16 +1366,12 @@ tenant_mxgemm_kernel(const int4v* __restrict__ a, const int4v* __restrict__ b,
   const uint32_t write_at = gemm_slot(load_row, load_c);  // + 32 rows: + 256
   const uint32_t scale_a_at = (64 * (wave >> 1) + r) * G::kWordBytes;
   const uint32_t scale_b_at = (64 * (wave & 1u) + r) * G::kWordBytes;
-  const auto window = [](const auto* first, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(first)),
-                                             0, static_cast<int>(bytes), kBufferWord3);
-  };
-  const auto ra = window(a + static_cast<uint64_t>(row0) * (row_bytes / 16),
-                         (s_rows - row0) * row_bytes);
-  const auto rb = window(b + static_cast<uint64_t>(col0) * (row_bytes / 16),
-                         (s_rows - col0) * row_bytes);
-  const auto rsa = window(sa + row0, (steps * s_rows - row0) * G::kWordBytes);
-  const auto rsb = window(sb + col0, (steps * s_rows - col0) * G::kWordBytes);
+  const auto ra = buffer_window(a + static_cast<uint64_t>(row0) * (row_bytes / 16),
+                                (s_rows - row0) * row_bytes);
+  const auto rb = buffer_window(b + static_cast<uint64_t>(col0) * (row_bytes / 16),
+                                (s_rows - col0) * row_bytes);
+  const auto rsa = buffer_window(sa + row0, (steps * s_rows - row0) * G::kWordBytes);
+  const auto rsb = buffer_window(sb + col0, (steps * s_rows - col0) * G::kWordBytes);
   // What this lane reads: rows 64 x (wave's half) + 32 t + r of either slab;
   // 32 t and 64 leave the row's key alone.
   const uint32_t read_a = (64 * (wave >> 1) + r) * kGemmRowVecs;
@@ -1502,34 +1492,6 @@ constexpr int kGemmDirectStages = GPUPROBE_GEMM_DIRECT_STAGES;
 static_assert(kGemmDirectStages == 2 || kGemmDirectStages == 3, "a ring of two or three");
 
 using LdsPtr = __attribute__((address_space(3))) void*;
-
-// One step's sixteen MFMAs of a wave on the slabs {A, B} of `from`: the
-// `multiply` of tenant_gemm_kernel as a function (that kernel keeps its own,
-// so that its code stays the one its figures were measured on). The lane
-// reads rows read_a / 8 and read_b / 8 (+ 32 t) of the slabs, chunk (2 s + h)
-// ^ read_key at sub-step s.
-__device__ inline void gemm_multiply(MfmaTile& acc, const int4v (*from)[kGemmSlabVecs],
-                                     uint32_t read_a, uint32_t read_b, uint32_t read_key,
-                                     uint32_t h) {
-  const auto read = [&](MfmaFrags<kBf16>& f, uint32_t s) {
-    const uint32_t c = (2 * s + h) ^ read_key;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      f.a[t] = __builtin_bit_cast(bf16x8, from[0][read_a + 32 * kGemmRowVecs * t + c]);
-      f.b[t] = __builtin_bit_cast(bf16x8, from[1][read_b + 32 * kGemmRowVecs * t + c]);
-    }
-  };
-  MfmaFrags<kBf16> f[2];
-  read(f[0], 0);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (uint32_t s = 0; s < 4; ++s) {
-    if (s < 3) read(f[(s + 1) & 1u], s + 1);
-    mfma_step(f[s & 1u], acc);
-    if (s < 3) mfma_lds_interleave<4, 2>();
-  }
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 // tenant_gemm_kernel's product from the same buffers with the slabs loaded
 // global memory -> LDS without passing through registers (the 16-byte LDS-DMA
@@ -1719,71 +1681,6 @@ __device__ constexpr uint32_t decode_chunk(uint32_t p, uint32_t h) {
   return F == kMxfp8 ? 2 * p + h : 4 * h + p;
 }
 
-// The operands of a decode tenant. `buf` is A (32 x K, row-major) followed by
-// W (N x K, row n holding column n of the product's right-hand side), the
-// elements of tenant_mxgemm_fill_kernel's A and B: one 16-byte store of 16 or
-// 32 elements per step, grid-stride, v16 = 8 x steps the stores of a row and
-// n16 = (32 + N) v16 those of both matrices. `scales` is step-major as there:
-// A's words [steps][32], then W's [steps][N], byte b of a word the scale of
-// the step's block b; nwords = (32 + N) x steps. All indices are 64-bit,
-// below n16 and below nwords. (A kernel of its own, so that the fill the
-// gemm kinds were measured with stays as it is.)
-template <int F>
-__global__ void __launch_bounds__(kBlock)
-tenant_decode_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint64_t v16,
-                          typename MxGemm<F>::Word* __restrict__ scales, uint64_t nwords,
-                          uint64_t n, uint32_t key) {
-  using G = MxGemm<F>;
-  constexpr uint32_t kPerDword = F == kMxfp8 ? 4 : 8;  // elements of one dword
-  const uint64_t first = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-  for (uint64_t i = first; i < n16; i += stride) {
-    const uint64_t line = i / v16;
-    const bool is_w = line >= kDecodeRows;
-    const uint32_t row = static_cast<uint32_t>((is_w ? line - kDecodeRows : line) % kGemmRowPeriod);
-    const uint32_t k0 = static_cast<uint32_t>((i % v16) * (4 * kPerDword) % kGemmKPeriod);
-    int4v v;
-#pragma unroll
-    for (uint32_t d = 0; d < 4; ++d) {
-      uint32_t word = 0;
-#pragma unroll
-      for (uint32_t q = 0; q < kPerDword; ++q) {
-        const uint32_t k = k0 + kPerDword * d + q;
-        const uint32_t hash = is_w ? mfma_b_hash<F>(key, k, row) : mfma_a_hash<F>(key, row, k);
-        if constexpr (F == kMxfp8)
-          word |= to_e4m3_bits(static_cast<int>(hash % 15u) - 7) << (8 * q);
-        else
-          word |= (hash & 15u) << (4 * q);
-      }
-      v[d] = static_cast<int>(word);
-    }
-    buf[i] = v;
-  }
-  const uint64_t a_words = nwords / (kDecodeRows + n) * kDecodeRows;  // steps x 32
-  for (uint64_t i = first; i < nwords; i += stride) {
-    const bool is_w = i >= a_words;
-    const uint64_t rows = is_w ? n : kDecodeRows, at = is_w ? i - a_words : i;
-    const uint32_t row = static_cast<uint32_t>((at % rows) % kGemmRowPeriod);
-    const uint32_t blk0 = static_cast<uint32_t>((at / rows) * G::kWordBytes % 3);
-    uint32_t word[2] = {0, 0};
-#pragma unroll
-    for (uint32_t b = 0; b < G::kWordBytes; ++b) {
-      const uint32_t blk = (blk0 + b) % 3;
-      uint32_t byte;
-      if constexpr (F == kMxfp8)
-        byte = 127u + (is_w ? mfma_b_scale_bit<F>(key, blk, row)
-                            : mfma_a_scale_bit<F>(key, row, blk));
-      else
-        byte = 128u + (is_w ? 0u : mfma_a_scale_bit<F>(key, row, blk));
-      word[b / 4] |= byte << (8 * (b % 4));
-    }
-    if constexpr (F == kMxfp8)
-      scales[i] = static_cast<int>(word[0]);
-    else
-      scales[i] = int2v{static_cast<int>(word[0]), static_cast<int>(word[1])};
-  }
-}
-
 // One step's loads of a lane, as they come from global memory: the scale
 // words of its weight row and of its row of A, its chunk of A's slab and the
 // four pieces of its weight row.
@@ -1963,16 +1860,12 @@ tenant_decode_kernel(const int4v* __restrict__ a, const int4v* __restrict__ w,
   const uint32_t w_at = (32 * wave + r) * row_bytes + 16 * decode_chunk<F>(0, h);
   const uint32_t a_at = r * row_bytes + 16 * decode_chunk<F>(wave, h);
   const uint32_t sw_at = (32 * wave + r) * G::kWordBytes, sa_at = r * G::kWordBytes;
-  const auto window = [](const auto* first, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(first)),
-                                             0, static_cast<int>(bytes), kBufferWord3);
-  };
-  const auto rw = window(w + static_cast<uint64_t>(tile) * kGemmTile * (row_bytes / 16),
-                         kGemmTile * row_bytes);
-  const auto ra = window(a, kDecodeRows * row_bytes);
-  const auto rsw = window(sw + tile * kGemmTile,
-                          ((steps - 1) * n_rows + kGemmTile) * G::kWordBytes);
-  const auto rsa = window(sa, steps * kDecodeRows * G::kWordBytes);
+  const auto rw = buffer_window(w + static_cast<uint64_t>(tile) * kGemmTile * (row_bytes / 16),
+                                kGemmTile * row_bytes);
+  const auto ra = buffer_window(a, kDecodeRows * row_bytes);
+  const auto rsw = buffer_window(sw + tile * kGemmTile,
+                                 ((steps - 1) * n_rows + kGemmTile) * G::kWordBytes);
+  const auto rsa = buffer_window(sa, steps * kDecodeRows * G::kWordBytes);
 
   DecodeFetch<F> p[D];
   // Nothing is scheduled across a pin: the loads keep the order they are
@@ -2079,25 +1972,65 @@ enum class Kind : int {
   kDecodeMxfp4
 };
 constexpr int kKinds = 10;
-// Per kind: name, workgroups per CU (chase: one, that is one wave per SIMD;
-// the gemms: none, their grid is the problem's), whether it reads a buffer
-// filled beforehand, whether it takes form and operands.
+// What a kind shares with others: nothing (plain), form and operands (mfma),
+// the bf16 GEMM, a block-scaled GEMM, or the decode shape of one.
+enum class Family : int { kPlain, kMfma, kGemm, kMxGemm, kDecode };
+// Per kind: the kind itself (the table is indexed by it), name, family, the
+// form a block-scaled kind implies (kBf16 otherwise), workgroups per CU
+// (chase: one, that is one wave per SIMD; the gemms: none, their grid is the
+// problem's), whether it reads a buffer filled beforehand, whether its
+// launches carry clocks.
 struct KindInfo {
+  Kind kind;
   const char* name;
-  int groups_per_cu;
-  bool reads, matrix;
+  Family family;
+  int form, groups_per_cu;
+  bool reads, clocks;
 };
 constexpr KindInfo kKindTable[kKinds] = {
-    {"fma", kGroupsPerCu, false, false},   {"stream", kGroupsPerCu, true, false},
-    {"cache", kCacheGroupsPerCu, true, false}, {"chase", 1, true, false},
-    {"mfma", kMfmaGroupsPerCu, false, true},   {"gemm", 0, true, false},
-    {"gemm-mxfp8", 0, true, false},            {"gemm-mxfp4", 0, true, false},
-    {"decode-mxfp8", 0, true, false},          {"decode-mxfp4", 0, true, false}};
+    {Kind::kFma, "fma", Family::kPlain, kBf16, kGroupsPerCu, false, false},
+    {Kind::kStream, "stream", Family::kPlain, kBf16, kGroupsPerCu, true, false},
+    {Kind::kCache, "cache", Family::kPlain, kBf16, kCacheGroupsPerCu, true, false},
+    {Kind::kChase, "chase", Family::kPlain, kBf16, 1, true, false},
+    {Kind::kMfma, "mfma", Family::kMfma, kBf16, kMfmaGroupsPerCu, false, true},
+    {Kind::kGemm, "gemm", Family::kGemm, kBf16, 0, true, true},
+    {Kind::kGemmMxfp8, "gemm-mxfp8", Family::kMxGemm, kMxfp8, 0, true, true},
+    {Kind::kGemmMxfp4, "gemm-mxfp4", Family::kMxGemm, kMxfp4, 0, true, true},
+    {Kind::kDecodeMxfp8, "decode-mxfp8", Family::kDecode, kMxfp8, 0, true, true},
+    {Kind::kDecodeMxfp4, "decode-mxfp4", Family::kDecode, kMxfp4, 0, true, true}};
+constexpr bool kind_table_in_order() {
+  for (int i = 0; i < kKinds; ++i)
+    if (static_cast<int>(kKindTable[i].kind) != i) return false;
+  return true;
+}
+static_assert(kind_table_in_order(), "row i of kKindTable describes kind i");
+constexpr const KindInfo& kind_info(Kind k) { return kKindTable[static_cast<int>(k)]; }
 
 // Whether a kind is one of the GEMMs, the decode-shaped ones included, and
 // whether a block-scaled one; the form of the latter is the kind's.
-constexpr bool is_gemm(Kind k) { return k >= Kind::kGemm; }
-constexpr bool is_mxgemm(Kind k) { return k > Kind::kGemm; }
+constexpr bool is_mxgemm(Kind k) {
+  return kind_info(k).family == Family::kMxGemm || kind_info(k).family == Family::kDecode;
+}
+constexpr bool is_gemm(Kind k) { return kind_info(k).family == Family::kGemm || is_mxgemm(k); }
+
+// What plan_tenant needs of a block-scaled form, from MxGemm<F>; by form.
+struct MxFormInfo {
+  int step_k, max_iters;
+  uint64_t word_bytes;
+};
+template <int F>
+constexpr MxFormInfo mx_form_of() {
+  return {MxGemm<F>::kStepK, MxGemm<F>::kMaxIters, MxGemm<F>::kWordBytes};
+}
+constexpr MxFormInfo kMxFormTable[kMfmaForms] = {
+    {}, {}, mx_form_of<kMxfp8>(), mx_form_of<kMxfp4>()};
+
+// Calls fn with a block-scaled form as a compile-time constant.
+template <class Fn>
+void with_mx_form(int form, Fn&& fn) {
+  if (form == kMxfp8) fn(std::integral_constant<int, kMxfp8>{});
+  else fn(std::integral_constant<int, kMxfp4>{});
+}
 
 // The kernel of an mfma tenant: [operands from LDS][form].
 using MfmaKernel = decltype(&tenant_mfma_kernel<kBf16>);
@@ -2165,6 +2098,16 @@ struct TenantResult {
   std::vector<unsigned long long> out, recs, clks;
 };
 
+// The end of a GEMM's plan, from m, n, k and the tiles of a pass: the passes
+// (0: the kind's default) clamped to the largest grid, the grid and the flops.
+void plan_gemm_grid(TenantResult& r, int tiles, int passes, int default_passes) {
+  r.tiles = tiles;
+  if (passes <= 0) passes = default_passes;
+  r.passes = std::min(passes, kGemmMaxGroups / r.tiles);
+  r.workgroups = r.tiles * r.passes;
+  r.work_per_launch = 2.0 * r.m * r.n * r.k * r.passes;
+}
+
 // Plan: what a call launches, from its arguments alone (no HIP call). The grid
 // depends on the card, never on the mask: the same work either way. (To a
 // process started under ROC_GLOBAL_CU_MASK the runtime reports only that mask's
@@ -2173,10 +2116,10 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
                          int form, bool lds, bool direct) {
   TenantResult r;
   r.kind = kind;
-  r.form = form;
+  r.form = is_mxgemm(kind) ? kind_info(kind).form : form;
   r.lds = lds;
   r.direct = direct;
-  r.workgroups = kKindTable[static_cast<int>(kind)].groups_per_cu * cus;
+  r.workgroups = kind_info(kind).groups_per_cu * cus;
   const double lanes = static_cast<double>(r.workgroups) * kBlock;
   const uint64_t waves = static_cast<uint64_t>(r.workgroups) * kWavesPerGroup;
   switch (kind) {
@@ -2228,11 +2171,7 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
       r.m = r.n = std::min<uint64_t>(std::max<uint64_t>(s, kGemmTile), kGemmMaxSide);
       r.bytes = 4 * r.m * r.k;  // A and B, two bytes an element
       r.side = static_cast<int>(r.m / kGemmTile);
-      r.tiles = r.side * r.side;
-      if (passes <= 0) passes = kGemmDefaultPasses;
-      r.passes = std::min(passes, kGemmMaxGroups / r.tiles);
-      r.workgroups = r.tiles * r.passes;
-      r.work_per_launch = 2.0 * r.m * r.n * r.k * r.passes;
+      plan_gemm_grid(r, r.side * r.side, passes, kGemmDefaultPasses);
       r.load_bytes_per_launch =
           static_cast<uint64_t>(r.workgroups) * 2 * kGemmTile * r.k * 2;
       if (direct)  // the ring of slab pairs and the reduction's words
@@ -2243,58 +2182,45 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
     case Kind::kGemmMxfp4: {
       // agent/cotenancy.py states the same rule on its own (gemm_shape). A
       // row of A plus one of B is 256 bytes a step in either form.
-      const bool f8 = kind == Kind::kGemmMxfp8;
-      r.form = f8 ? kMxfp8 : kMxfp4;
-      const int step_k = f8 ? MxGemm<kMxfp8>::kStepK : MxGemm<kMxfp4>::kStepK;
-      const uint64_t word = f8 ? MxGemm<kMxfp8>::kWordBytes : MxGemm<kMxfp4>::kWordBytes;
-      if (iters <= 0) iters = 4096 / step_k;
-      r.iters = std::min(iters, f8 ? MxGemm<kMxfp8>::kMaxIters : MxGemm<kMxfp4>::kMaxIters);
-      r.k = static_cast<uint64_t>(step_k) * r.iters;
+      const MxFormInfo& mx = kMxFormTable[r.form];
+      if (iters <= 0) iters = 4096 / mx.step_k;
+      r.iters = std::min(iters, mx.max_iters);
+      r.k = static_cast<uint64_t>(mx.step_k) * r.iters;
       const uint64_t s = bytes == 0 ? kMxGemmDefaultSide
                                     : bytes / (256ULL * r.iters) / kGemmTile * kGemmTile;
       r.m = r.n = std::min<uint64_t>(std::max<uint64_t>(s, kGemmTile), kGemmMaxSide);
       r.bytes = 256 * r.m * r.iters;
-      r.scale_bytes = 2 * r.m * r.iters * word;
+      r.scale_bytes = 2 * r.m * r.iters * mx.word_bytes;
       r.side = static_cast<int>(r.m / kGemmTile);
-      r.tiles = r.side * r.side;
-      if (passes <= 0) passes = kMxGemmDefaultPasses[r.form];
-      r.passes = std::min(passes, kGemmMaxGroups / r.tiles);
-      r.workgroups = r.tiles * r.passes;
-      r.work_per_launch = 2.0 * r.m * r.n * r.k * r.passes;
+      plan_gemm_grid(r, r.side * r.side, passes, kMxGemmDefaultPasses[r.form]);
       // Per workgroup and step two slabs of 16 KiB, and per wave the words of
       // its 64 rows of A and 64 of B (lanes r and r + 32 ask for the same one).
-      r.load_bytes_per_launch = static_cast<uint64_t>(r.workgroups) * r.iters *
-                                (2 * kGemmSlabVecs * 16 + kWavesPerGroup * kGemmTile * word);
+      r.load_bytes_per_launch =
+          static_cast<uint64_t>(r.workgroups) * r.iters *
+          (2 * kGemmSlabVecs * 16 + kWavesPerGroup * kGemmTile * mx.word_bytes);
       break;
     }
     case Kind::kDecodeMxfp8:
     case Kind::kDecodeMxfp4: {
       // agent/cotenancy.py states the same rule on its own (decode_shape). A
       // row is 128 bytes a step in either form.
-      const bool f8 = kind == Kind::kDecodeMxfp8;
-      r.form = f8 ? kMxfp8 : kMxfp4;
-      const int step_k = f8 ? MxGemm<kMxfp8>::kStepK : MxGemm<kMxfp4>::kStepK;
-      const uint64_t word = f8 ? MxGemm<kMxfp8>::kWordBytes : MxGemm<kMxfp4>::kWordBytes;
-      if (iters <= 0) iters = kDecodeDefaultK / step_k;
-      r.iters = std::min(iters, f8 ? MxGemm<kMxfp8>::kMaxIters : MxGemm<kMxfp4>::kMaxIters);
-      r.k = static_cast<uint64_t>(step_k) * r.iters;
+      const MxFormInfo& mx = kMxFormTable[r.form];
+      if (iters <= 0) iters = kDecodeDefaultK / mx.step_k;
+      r.iters = std::min(iters, mx.max_iters);
+      r.k = static_cast<uint64_t>(mx.step_k) * r.iters;
       if (bytes == 0) bytes = kGiB;  // more than the Infinity Cache holds
       const uint64_t n = bytes / (128ULL * r.iters) / kGemmTile * kGemmTile;
       r.m = kDecodeRows;
       r.n = std::min<uint64_t>(std::max<uint64_t>(n, kGemmTile), kDecodeMaxN);
       r.bytes = 128 * r.n * r.iters;  // W's elements
       r.lead_bytes = 128ULL * kDecodeRows * r.iters;
-      r.scale_bytes = (kDecodeRows + r.n) * r.iters * word;
-      r.tiles = static_cast<int>(r.n / kGemmTile);
-      if (passes <= 0) passes = kDecodeDefaultPasses[r.form];
-      r.passes = std::min(passes, kGemmMaxGroups / r.tiles);
-      r.workgroups = r.tiles * r.passes;
-      r.work_per_launch = 2.0 * r.m * r.n * r.k * r.passes;
+      r.scale_bytes = (kDecodeRows + r.n) * r.iters * mx.word_bytes;
+      plan_gemm_grid(r, static_cast<int>(r.n / kGemmTile), passes, kDecodeDefaultPasses[r.form]);
       // Per workgroup and step 16 KiB of W, the 4 KiB slab of A, and per wave
       // the words of its 32 rows of W and of the 32 of A.
       r.load_bytes_per_launch =
           static_cast<uint64_t>(r.workgroups) * r.iters *
-          (kGemmTile * 128 + kDecodeRows * 128 + 2 * kWavesPerGroup * kDecodeRows * word);
+          (kGemmTile * 128 + kDecodeRows * 128 + 2 * kWavesPerGroup * kDecodeRows * mx.word_bytes);
       break;
     }
   }
@@ -2315,23 +2241,15 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
   // One record {~0, 0} per timed launch, and one more for the warm-up.
   recs.h.assign(2 * static_cast<size_t>(launches + 1), 0ULL);
   for (size_t i = 0; i < recs.h.size(); i += 2) recs.h[i] = ~0ULL;
-  if (kKindTable[static_cast<int>(r.kind)].reads) buf.alloc(r.lead_bytes + r.bytes);
+  if (kind_info(r.kind).reads) buf.alloc(r.lead_bytes + r.bytes);
   if (is_mxgemm(r.kind)) scales.alloc(r.scale_bytes);
-  switch (r.kind) {  // what a lane stores, and what else a launch records
-    case Kind::kFma:
-      out.alloc(lanes * sizeof(float));
-      break;
-    case Kind::kMfma:  // {sum of shader cycles, sum of wall ticks}, from zero
-    case Kind::kGemm:
-    case Kind::kGemmMxfp8:
-    case Kind::kGemmMxfp4:
-    case Kind::kDecodeMxfp8:
-    case Kind::kDecodeMxfp4:
-      clks.h.assign(recs.h.size(), 0ULL);
-      [[fallthrough]];
-    default:
-      r.out.resize(lanes);
-      out.alloc(lanes * sizeof(unsigned long long));
+  // {sum of shader cycles, sum of wall ticks} per launch, from zero.
+  if (kind_info(r.kind).clocks) clks.h.assign(recs.h.size(), 0ULL);
+  if (r.kind == Kind::kFma) {  // what a lane stores
+    out.alloc(lanes * sizeof(float));
+  } else {
+    r.out.resize(lanes);
+    out.alloc(lanes * sizeof(unsigned long long));
   }
   recs.copy(true);
   clks.copy(true);
@@ -2346,19 +2264,14 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
       HIP_CHECK(hipGetLastError());
     };
     unsigned long long* const o64 = out.as<unsigned long long>();
-    // A, then B behind it; A's scale words, then B's behind them.
-    const auto mxgemm = [&](auto kernel, auto* words, unsigned long long* rec,
-                            unsigned long long* clk) {
-      go(grid, kernel, buf.as<const int4v>(), buf.as<const int4v>() + n16 / 2, words,
-         words + r.m * r.iters, static_cast<uint32_t>(r.side), static_cast<uint32_t>(r.iters),
-         o64, rec, clk);
-    };
-    // A, then W behind it; A's scale words, then W's behind them.
-    const auto decode = [&](auto kernel, auto* words, unsigned long long* rec,
-                            unsigned long long* clk) {
-      go(grid, kernel, buf.as<const int4v>(), buf.as<const int4v>() + r.lead_bytes / 16, words,
-         words + kDecodeRows * r.iters, static_cast<uint32_t>(r.tiles),
-         static_cast<uint32_t>(r.iters), o64, rec, clk);
+    // A launch of a block-scaled form's `kernel`: A, then B (decode: W) behind
+    // A's r.m rows of 128 bytes a step; A's scale words, then B's behind them.
+    const auto mx_go = [&](auto form, auto kernel, int shape, unsigned long long* rec,
+                           unsigned long long* clk) {
+      const auto* a = buf.as<const int4v>();
+      const auto* words = scales.as<const typename MxGemm<decltype(form)::value>::Word>();
+      go(grid, kernel, a, a + r.m * r.iters * kGemmRowVecs, words, words + r.m * r.iters,
+         static_cast<uint32_t>(shape), static_cast<uint32_t>(r.iters), o64, rec, clk);
     };
     const auto launch = [&](int slot) {
       unsigned long long* rec = recs.at(2 * slot);
@@ -2386,32 +2299,20 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
              clks.at(2 * slot));
           break;
         case Kind::kGemmMxfp8:
-          mxgemm(tenant_mxgemm_kernel<kMxfp8>, scales.as<const int>(), rec, clks.at(2 * slot));
-          break;
         case Kind::kGemmMxfp4:
-          mxgemm(tenant_mxgemm_kernel<kMxfp4>, scales.as<const int2v>(), rec,
-                 clks.at(2 * slot));
+          with_mx_form(r.form, [&](auto form) {
+            mx_go(form, tenant_mxgemm_kernel<decltype(form)::value>, r.side, rec,
+                  clks.at(2 * slot));
+          });
           break;
         case Kind::kDecodeMxfp8:
-          decode(tenant_decode_kernel<kMxfp8>, scales.as<const int>(), rec, clks.at(2 * slot));
-          break;
         case Kind::kDecodeMxfp4:
-          decode(tenant_decode_kernel<kMxfp4>, scales.as<const int2v>(), rec,
-                 clks.at(2 * slot));
+          with_mx_form(r.form, [&](auto form) {
+            mx_go(form, tenant_decode_kernel<decltype(form)::value>, r.tiles, rec,
+                  clks.at(2 * slot));
+          });
           break;
       }
-    };
-    // The fill of a decode tenant: A's and W's elements, then their scale words.
-    const auto decode_fill = [&](auto kernel, auto* words) {
-      go(dim3(kGroupsPerCu * cus), kernel, buf.as<int4v>(), n16,
-         static_cast<uint64_t>(r.iters) * kGemmRowVecs, words, (kDecodeRows + r.n) * r.iters,
-         r.n, mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
-    };
-    // The fill of a block-scaled gemm: elements, then A's and B's scale words.
-    const auto mxfill = [&](auto kernel, auto* words) {
-      go(dim3(kGroupsPerCu * cus), kernel, buf.as<int4v>(), n16,
-         static_cast<uint64_t>(r.iters) * kGemmRowVecs, words, 2 * r.m * r.iters, r.m,
-         mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
     };
     switch (r.kind) {  // the fill
       case Kind::kStream:
@@ -2426,19 +2327,20 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
         go(dim3(kGroupsPerCu * cus), tenant_gemm_fill_kernel, buf.as<int4v>(), n16, r.k / 8,
            mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
         break;
-      case Kind::kGemmMxfp8:
-        mxfill(tenant_mxgemm_fill_kernel<kMxfp8>, scales.as<int>());
-        break;
+      case Kind::kGemmMxfp8:  // elements, then the scale words; r.m and r.n rows
       case Kind::kGemmMxfp4:
-        mxfill(tenant_mxgemm_fill_kernel<kMxfp4>, scales.as<int2v>());
-        break;
       case Kind::kDecodeMxfp8:
-        decode_fill(tenant_decode_fill_kernel<kMxfp8>, scales.as<int>());
-        break;
       case Kind::kDecodeMxfp4:
-        decode_fill(tenant_decode_fill_kernel<kMxfp4>, scales.as<int2v>());
+        with_mx_form(r.form, [&](auto form) {
+          constexpr int F = decltype(form)::value;
+          go(dim3(kGroupsPerCu * cus), tenant_mxgemm_fill_kernel<F>, buf.as<int4v>(), n16,
+             static_cast<uint64_t>(r.iters) * kGemmRowVecs,
+             scales.as<typename MxGemm<F>::Word>(), (r.m + r.n) * r.iters, r.m, r.n,
+             mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
+        });
         break;
-      default:
+      case Kind::kFma:
+      case Kind::kMfma:
         break;
     }
     // Warm-up, not timed: the same launch once, so that the code object is
@@ -2479,41 +2381,31 @@ void summarise(TenantResult& r) {
     rates.push_back(e.rate);
   }
   r.rate = median(rates);
-  switch (r.kind) {
-    case Kind::kFma:
-      break;
-    case Kind::kStream:
-    case Kind::kCache:
-      for (unsigned long long w : r.out) r.checksum ^= w;
-      break;
-    case Kind::kChase:
-      // Every lane's end node weighted by its global index, both from 1 so
-      // that neither lane 0 nor node 0 drops out.
-      for (size_t g = 0; g < r.out.size(); ++g) r.checksum += (g + 1) * (r.out[g] + 1);
-      for (const auto& e : r.launches) own.push_back(e.seconds * 1e9 / r.iters);
-      r.ns_per_hop = median(own);
-      break;
-    case Kind::kMfma:  // every lane's fold weighted likewise
-    case Kind::kGemm:  // every workgroup's word weighted by its pass, from 1
-    case Kind::kGemmMxfp8:
-    case Kind::kGemmMxfp4:
-    case Kind::kDecodeMxfp8:
-    case Kind::kDecodeMxfp4:
-      for (size_t g = 0; g < r.out.size(); ++g)
-        r.checksum += (is_gemm(r.kind) ? 1 + g / r.tiles : g + 1) * r.out[g];
-      for (size_t l = 0; l < r.launches.size(); ++l) {
-        Launch& e = r.launches[l];
-        e.cycles = r.clks[2 * l];
-        e.ticks = r.clks[2 * l + 1];
-        if (e.ticks == 0)
-          throw std::runtime_error("cu_tenant_run: launch " + std::to_string(l) +
-                                   " left no usable cycle record");
-        e.clock_ghz = static_cast<double>(e.cycles) / static_cast<double>(e.ticks) *
-                      r.tick_hz / 1e9;
-        own.push_back(e.clock_ghz);
-      }
-      r.clock_ghz = median(own);
-      break;
+  if (kind_info(r.kind).clocks) {
+    // mfma: every lane's fold weighted by its global index, from 1; the GEMMs:
+    // every workgroup's word weighted by its pass, from 1.
+    for (size_t g = 0; g < r.out.size(); ++g)
+      r.checksum += (is_gemm(r.kind) ? 1 + g / r.tiles : g + 1) * r.out[g];
+    for (size_t l = 0; l < r.launches.size(); ++l) {
+      Launch& e = r.launches[l];
+      e.cycles = r.clks[2 * l];
+      e.ticks = r.clks[2 * l + 1];
+      if (e.ticks == 0)
+        throw std::runtime_error("cu_tenant_run: launch " + std::to_string(l) +
+                                 " left no usable cycle record");
+      e.clock_ghz = static_cast<double>(e.cycles) / static_cast<double>(e.ticks) *
+                    r.tick_hz / 1e9;
+      own.push_back(e.clock_ghz);
+    }
+    r.clock_ghz = median(own);
+  } else if (r.kind == Kind::kChase) {
+    // Every lane's end node weighted by its global index, both from 1 so
+    // that neither lane 0 nor node 0 drops out.
+    for (size_t g = 0; g < r.out.size(); ++g) r.checksum += (g + 1) * (r.out[g] + 1);
+    for (const auto& e : r.launches) own.push_back(e.seconds * 1e9 / r.iters);
+    r.ns_per_hop = median(own);
+  } else {  // stream and cache; fma leaves no words
+    for (unsigned long long w : r.out) r.checksum ^= w;
   }
 }
 
@@ -2526,7 +2418,7 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
       raw_mask.empty() ? MaskWords{} : gpuprobe::fit_mask(raw_mask, cus);
   launches = std::min(std::max(launches, 1), kMaxLaunches);
   TenantResult r = plan_tenant(kind, cus, iters, bytes, passes, form, lds, direct);
-  if (kKindTable[static_cast<int>(kind)].reads) {
+  if (kind_info(kind).reads) {
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     r.free_bytes = free_b;
@@ -2556,17 +2448,20 @@ void register_cotenant(py::module_& m) {
         const MaskWords words = gpuprobe::mask_from_python(mask);
         int k = 0;
         while (k < kKinds && kind != kKindTable[k].name) ++k;
-        if (k == kKinds)
-          throw py::value_error(
-              "cu_tenant_run: kind must be \"fma\", \"stream\", \"cache\", "
-              "\"chase\", \"mfma\", \"gemm\", \"gemm-mxfp8\", \"gemm-mxfp4\", "
-              "\"decode-mxfp8\" or \"decode-mxfp4\"");
+        if (k == kKinds) {
+          std::string names;  // "a", "b", ... "y" or "z"
+          for (int i = 0; i < kKinds; ++i)
+            names += std::string(i == 0 ? "\"" : i + 1 < kKinds ? ", \"" : " or \"") +
+                     kKindTable[i].name + "\"";
+          throw py::value_error("cu_tenant_run: kind must be " + names);
+        }
+        const bool matrix = kKindTable[k].family == Family::kMfma;  // takes form and operands
         int f = 0;
         while (f < kMfmaForms && form != kMfmaFormTable[f].name) ++f;
         if (f == kMfmaForms)
           throw py::value_error(
               "cu_tenant_run: form must be \"bf16\", \"fp8\", \"mxfp8\" or \"mxfp4\"");
-        if (f != kBf16 && !kKindTable[k].matrix)
+        if (f != kBf16 && !matrix)
           throw py::value_error(
               "cu_tenant_run: form \"" + form + "\" needs kind \"mfma\"; of the forms "
               "\"bf16\", \"fp8\", \"mxfp8\" and \"mxfp4\" every other kind takes only "
@@ -2575,7 +2470,7 @@ void register_cotenant(py::module_& m) {
           throw py::value_error(
               "cu_tenant_run: operands must be \"registers\" or \"lds\"");
         const bool lds = operands == "lds";
-        if (lds && !kKindTable[k].matrix)
+        if (lds && !matrix)
           throw py::value_error(
               "cu_tenant_run: operands \"lds\" needs kind \"mfma\"; of the operands "
               "\"registers\" and \"lds\" every other kind takes only \"registers\"");
@@ -2603,29 +2498,28 @@ void register_cotenant(py::module_& m) {
         d["applied_mask"] = gpuprobe::mask_to_python(r.applied);
         d["tick_hz"] = r.tick_hz;
         d["workgroups"] = r.workgroups;
-        // The kind's keys, whether a launch has clocks, what follows the rate.
+        // The kind's keys; `last`: what follows the rate.
         py::dict last;
-        bool clocks = false;
-        switch (r.kind) {
-          case Kind::kFma:
-            d["iters"] = r.iters;
+        const bool clocks = kind_info(r.kind).clocks;
+        switch (kind_info(r.kind).family) {
+          case Family::kPlain:
+            if (r.kind == Kind::kFma) {
+              d["iters"] = r.iters;
+            } else if (r.kind == Kind::kStream || r.kind == Kind::kCache) {
+              d["bytes"] = r.bytes;
+              d["passes"] = r.passes;
+              d["checksum"] = r.checksum;
+              if (r.kind == Kind::kCache) d["bytes_per_cu"] = r.bytes_per_cu;
+            } else {  // chase
+              d["bytes"] = r.bytes;
+              d["nodes"] = r.nodes;
+              d["stride"] = r.stride;
+              d["iters"] = r.iters;
+              d["checksum"] = r.checksum;
+              last["ns_per_hop"] = r.ns_per_hop;
+            }
             break;
-          case Kind::kStream:
-          case Kind::kCache:
-            d["bytes"] = r.bytes;
-            d["passes"] = r.passes;
-            d["checksum"] = r.checksum;
-            if (r.kind == Kind::kCache) d["bytes_per_cu"] = r.bytes_per_cu;
-            break;
-          case Kind::kChase:
-            d["bytes"] = r.bytes;
-            d["nodes"] = r.nodes;
-            d["stride"] = r.stride;
-            d["iters"] = r.iters;
-            d["checksum"] = r.checksum;
-            last["ns_per_hop"] = r.ns_per_hop;
-            break;
-          case Kind::kMfma:
+          case Family::kMfma:
             d["form"] = kMfmaFormTable[r.form].name;
             d["iters"] = r.iters;
             d["checksum"] = r.checksum;
@@ -2634,14 +2528,10 @@ void register_cotenant(py::module_& m) {
               d["lds_bytes"] = r.lds_bytes;
               d["lds_bytes_per_launch"] = r.lds_bytes_per_launch;
             }
-            clocks = true;
-            last["clock_ghz"] = r.clock_ghz;
             break;
-          case Kind::kGemm:
-          case Kind::kGemmMxfp8:
-          case Kind::kGemmMxfp4:
-          case Kind::kDecodeMxfp8:
-          case Kind::kDecodeMxfp4:
+          case Family::kGemm:
+          case Family::kMxGemm:
+          case Family::kDecode:
             if (is_mxgemm(r.kind)) d["form"] = kMfmaFormTable[r.form].name;
             d["m"] = r.m;
             d["n"] = r.n;
@@ -2656,10 +2546,9 @@ void register_cotenant(py::module_& m) {
               d["stages"] = kGemmDirectStages;
               d["lds_bytes"] = r.lds_bytes;
             }
-            clocks = true;
-            last["clock_ghz"] = r.clock_ghz;
             break;
         }
+        if (clocks) last["clock_ghz"] = r.clock_ghz;
         d["work_per_launch"] = r.work_per_launch;
         py::list launches_out;
         for (const auto& e : r.launches) {
