@@ -438,7 +438,7 @@ class NodeAgent:
         containers are wired: each tenant's FMA and HBM-stream rate alone and
         while the other runs (cotenancy.isolation_report, to which `window`
         is passed: pairs, launches, iters, bytes, passes, timeout, windows,
-        form, operands, loads).
+        form, operands, loads, weights).
         Returns that report plus "tenants": [{core, mask, cus}].
 
         pairs=cotenancy.CACHE_PAIRS brings in the third kind, a tenant that
@@ -484,6 +484,11 @@ class NodeAgent:
         prefill gemm kind, both ways round: the tenant that loads the
         matrix cores and HBM together. Its entries carry the clock and its
         split too, and it takes neither form nor operands nor loads.
+        weights= (one of cotenancy.DECODE_WEIGHTS: "rows", "tiled") says how
+        the decode tenants' weight matrix lies in memory: "tiled" is the
+        same matrix shuffled once into the order the waves consume it, as
+        production decode GEMMs keep their weights, so that every load
+        instruction reads whole lines; their entries then add "weights".
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched

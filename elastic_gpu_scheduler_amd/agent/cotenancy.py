@@ -76,8 +76,15 @@ workgroup's waves through LDS. Their window is `bytes` (W's elements, 0: 1
 GiB, more than the Infinity Cache holds), `iters` (steps of 128 or 256 k, 0:
 K = 8192) and `passes` (whole re-reads of W); decode_shape() states the
 shape and gemm_checksum(32, n, k, ...) is the oracle unchanged. They take
-neither form nor operands nor loads. TENANT_KINDS stays the kinds before
-them; CO_KINDS is every kind a child can be started as.
+neither form nor operands nor loads. W lies in memory in one of two ways
+(DECODE_WEIGHTS): "rows", row-major, where every lane of a weight load sits
+on a row of its own and one wave instruction touches 32 lines of 128 bytes
+for 1 KiB, or "tiled", the 16-byte chunks stored once in the order a wave
+consumes them (units of 32 rows x one step, 4 KiB), where it reads 8 whole
+lines and a wave's K is one contiguous run: what production decode GEMMs on
+this chip do with their weights offline. The elements, the scales, the
+product and so the checksum are the same. TENANT_KINDS stays the kinds
+before them; CO_KINDS is every kind a child can be started as.
 
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
@@ -358,15 +365,22 @@ def _mfma_lane_sums(seed32: int, form: int = 0) -> Tuple[Tuple[int, ...], ...]:
 # How a gemm tenant's slabs reach LDS: through registers, or straight from
 # memory with the LDS-DMA load.
 GEMM_LOADS = ("registers", "direct")
-# What an mfma or a gemm tenant may be told beyond its window, in the order
-# its child is told, each with the values it may take and the kinds it is for.
-_MFMA_OPTIONS = {"form": MFMA_FORMS, "operands": MFMA_OPERANDS, "loads": GEMM_LOADS}
-_OPTION_KINDS = {"form": MATRIX_KINDS, "operands": MATRIX_KINDS, "loads": GEMM_KINDS}
+# How a decode tenant's weights lie in memory: row-major, or shuffled once
+# into the order its waves consume them.
+DECODE_WEIGHTS = ("rows", "tiled")
+# What an mfma, a gemm or a decode tenant may be told beyond its window, in
+# the order its child is told, each with the values it may take and the kinds
+# it is for.
+_MFMA_OPTIONS = {"form": MFMA_FORMS, "operands": MFMA_OPERANDS, "loads": GEMM_LOADS,
+                 "weights": DECODE_WEIGHTS}
+_OPTION_KINDS = {"form": MATRIX_KINDS, "operands": MATRIX_KINDS, "loads": GEMM_KINDS,
+                 "weights": DECODE_KINDS}
 
 
 def _checked(key: str, value: Optional[str]) -> str:
     if value not in _MFMA_OPTIONS[key]:
-        raise ValueError(f"unknown {_OPTION_KINDS[key][0]} {key} {value!r}: one of "
+        whose = _OPTION_KINDS[key][0].split("-")[0]  # mfma, gemm or decode
+        raise ValueError(f"unknown {whose} {key} {value!r}: one of "
                          + ", ".join(_MFMA_OPTIONS[key]))
     return value
 
@@ -543,6 +557,7 @@ def _child_parser() -> argparse.ArgumentParser:
     p.add_argument("--form", choices=MFMA_FORMS, default="bf16")
     p.add_argument("--operands", choices=MFMA_OPERANDS, default=None)
     p.add_argument("--loads", choices=GEMM_LOADS, default=None)
+    p.add_argument("--weights", choices=DECODE_WEIGHTS, default=None)
     return p
 
 
@@ -569,6 +584,9 @@ def child_main(argv: Optional[Sequence[str]] = None, stdin=None, stdout=None) ->
     # And the gemm kind's loads: the probe refuses "direct" beside another kind.
     if args.loads is not None:
         window["loads"] = args.loads
+    # And the decode kinds' weights: the probe refuses "tiled" beside another kind.
+    if args.weights is not None:
+        window["weights"] = args.weights
     warm = probe.cu_tenant_run(args.device, None, launches=1, **window)
     if "skipped" in warm:
         print(f"cotenancy child: {warm}", file=sys.stderr)
@@ -664,7 +682,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
              spawn: Optional[Callable[[List[str], Dict[str, str]], Any]] = None,
              form: Optional[str] = None,
              operands: Optional[str] = None,
-             loads: Optional[str] = None) -> Dict[str, Any]:
+             loads: Optional[str] = None,
+             weights: Optional[str] = None) -> Dict[str, Any]:
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
     "fma" | "stream" | "cache" | "chase" | "mfma" | "gemm" | "gemm-mxfp8" |
@@ -698,6 +717,14 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     are, and a child is given --loads, after --operands, only when one was
     named for it.
 
+    `weights` (one of DECODE_WEIGHTS) says how every decode tenant of the
+    call finds its weight matrix in memory, by the same rules once more: a
+    decode tenant may carry its own "weights" instead, an unknown value or
+    "weights" on a tenant of any other kind raises ValueError before
+    anything is started, the call-wide value leaves the other kinds as they
+    are, and a child is given --weights, after --loads, only when one was
+    named for it.
+
     Each child has `timeout` seconds from its start. The first child that
     times out, exits non-zero or prints no TENANT line ends the run: the
     others are killed and {"ok": False, "reason": "child-failed", "detail"}
@@ -706,7 +733,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
         raise ValueError("run_pair takes one or two tenants")
     if kinds is not None and len(kinds) != len(tenants):
         raise ValueError("one kind per tenant")
-    call = {"form": form, "operands": operands, "loads": loads}
+    call = {"form": form, "operands": operands, "loads": loads, "weights": weights}
     for key, value in call.items():
         if value is not None:
             _checked(key, value)
@@ -798,10 +825,11 @@ _SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",), "gemm": ("clock_
 
 
 def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
-              operands=None, loads=None) -> Optional[int]:
+              operands=None, loads=None, weights=None) -> Optional[int]:
     """The checksum a child's result must carry by the oracle of its kind
     (`pattern` is the reading kinds'); None for a kind that has none. A gemm
-    tenant's `loads` do not enter it: the product is the same."""
+    tenant's `loads` and a decode tenant's `weights` do not enter it: the
+    product is the same."""
     kind = result["kind"]
     if kind in READING_KINDS:
         return pattern(seed, int(result["bytes"]))
@@ -830,7 +858,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
                      windows: Optional[Mapping[str, Mapping[str, int]]] = None,
                      form: Optional[str] = None,
                      operands: Optional[str] = None,
-                     loads: Optional[str] = None) -> Dict[str, Any]:
+                     loads: Optional[str] = None,
+                     weights: Optional[str] = None) -> Dict[str, Any]:
     """Each of two tenants' ({"mask": int}) rate alone and next to the other.
 
     First one solo run per tenant and kind that `pairs` uses, then the pairs
@@ -921,6 +950,17 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     a pair, add "loads". With none named anywhere the children are started
     as before and no entry has "loads".
 
+    `weights` (one of DECODE_WEIGHTS, anything else raises ValueError) says
+    how the decode tenants' weight matrix lies in memory, alone and in every
+    pair: "rows", row-major, or "tiled", shuffled once into the order the
+    waves consume it, as production decode GEMMs keep their weights, so that
+    every load instruction reads whole lines; a tenant ({"mask": int,
+    "weights": str}) may name its own instead. The other kinds are not
+    touched by it. The checksum stays gemm_checksum(32, n, k, ..., form=)'s,
+    and the decode entries, solo and in a pair, add "weights". With none
+    named anywhere the children are started as before and no entry has
+    "weights".
+
     ok says that the measurement is valid (every child exited 0, every
     stream and cache checksum equals the pattern's, every chase, mfma and
     gemm checksum the closed form's, overlap was reached), not that the
@@ -940,7 +980,8 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     # Per option and tenant, what the tenant is started with as a tenant of
     # the option's kind.
     named = {key: [_mfma_option(key, t, _OPTION_KINDS[key][0], wide) for t in tenants]
-             for key, wide in (("form", form), ("operands", operands), ("loads", loads))}
+             for key, wide in (("form", form), ("operands", operands), ("loads", loads),
+                               ("weights", weights))}
     # The pattern's oracle, asked once per size.
     pattern = functools.lru_cache(maxsize=None)(expected_checksum or _pattern_checksum)
     window = {"iters": iters, "bytes": bytes, "passes": passes, "seed": seed,

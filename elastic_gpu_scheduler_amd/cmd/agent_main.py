@@ -32,7 +32,9 @@ bf16 GEMM whose operands travel global memory -> LDS -> MFMA;
 --co-tenancy-gemm-loads direct the bf16 one with its slabs loaded straight
 from memory into LDS. --co-tenancy-decode runs the decode shape of the
 block-scaled GEMM, 32 token rows against a weight matrix streamed from
-memory, beside itself, the streamer and the prefill GEMM.
+memory, beside itself, the streamer and the prefill GEMM;
+--co-tenancy-decode-weights tiled gives it its weights pre-shuffled into the
+order its waves consume them, as production decode GEMMs keep theirs.
 """
 from __future__ import annotations
 
@@ -218,6 +220,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "cycle_ratio; not together with --co-tenancy-cache, "
                         "--co-tenancy-chase, --co-tenancy-mfma or "
                         "--co-tenancy-gemm")
+    p.add_argument("--co-tenancy-decode-weights", choices=("rows", "tiled"),
+                   default=None,
+                   help="with --co-tenancy-decode: how the decode tenants' "
+                        "weight matrix lies in memory: rows (row-major, what "
+                        "they read when the flag is absent), or tiled, "
+                        "shuffled once into the order the waves consume it, "
+                        "so that every load instruction reads whole lines and "
+                        "a wave's K is one contiguous run, as production "
+                        "decode GEMMs on gfx950 keep their weights")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -260,7 +271,8 @@ def main(argv=None) -> int:
              ("--co-tenancy-gemm-form",)),
             ("--co-tenancy-decode", "--co-tenancy",
              ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma",
-              "--co-tenancy-gemm"))):
+              "--co-tenancy-gemm")),
+            ("--co-tenancy-decode-weights", "--co-tenancy-decode", ())):
         if not given(flag):
             continue
         if not given(needs):
@@ -282,6 +294,8 @@ def main(argv=None) -> int:
         if args.co_tenancy_decode is not None:
             each = {form: {"pairs": decode_pairs("decode-" + form)}
                     for form in args.co_tenancy_decode}
+            if args.co_tenancy_decode_weights is not None:
+                common["weights"] = args.co_tenancy_decode_weights
         elif args.co_tenancy_gemm_form is not None:
             each = {form: {"pairs": mxgemm_pairs("gemm-" + form)}
                     for form in args.co_tenancy_gemm_form}

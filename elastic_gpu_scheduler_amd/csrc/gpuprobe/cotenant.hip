@@ -1089,6 +1089,13 @@ struct MxGemm {
 constexpr int kMxGemmDefaultSide = 8192;
 constexpr int kMxGemmDefaultPasses[kMfmaForms] = {0, 0, 32, 64};
 
+// Which 16-byte chunk (0..7) of a row's 128-byte step lane half h holds in
+// piece p (0..3) of its registers; see tenant_decode_kernel.
+template <int F>
+__device__ constexpr uint32_t decode_chunk(uint32_t p, uint32_t h) {
+  return F == kMxfp8 ? 2 * p + h : 4 * h + p;
+}
+
 // The operands of a block-scaled gemm or decode tenant. `buf` is A (rows_a x
 // K, row-major) followed by B (rows_b x K, row n holding column n), S and S
 // rows for the gemm kinds, 32 and N for decode (whose B is W); e4m3 bytes or
@@ -1106,7 +1113,18 @@ constexpr int kMxGemmDefaultPasses[kMfmaForms] = {0, 0, 32, 64};
 // bit. So the 32 rows of a fragment are 128 or 256 contiguous bytes. nwords =
 // (rows_a + rows_b) x steps. All indices are 64-bit, below n16 and below
 // nwords.
-template <int F>
+//
+// kTiled (decode's weights = "tiled", rows_b a multiple of 32) stores B's
+// 16-byte chunks in the order tenant_decode_kernel's waves consume them and
+// leaves A and the scale words as they are. The unit is a row block of 32
+// rows x one step, 256 chunks, 4 KiB; units go row-block-major, then by step;
+// inside a unit chunk [piece p][lane l = r + 32 h] is chunk decode_chunk<F>(p,
+// h) of the step of row 32 block + r. Store index j = i - rows_a v16 of B is
+// unit j / 256 = block x steps + step, p = (j % 256) / 64 and l = j % 64; it is
+// mapped back to its row and its chunk 8 step + decode_chunk of the row before
+// hashing, a bijection of B's rows_b v16 indices, so that the same elements
+// are stored, one store per index, each below n16.
+template <int F, bool kTiled = false>
 __global__ void __launch_bounds__(kBlock)
 tenant_mxgemm_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint64_t v16,
                           typename MxGemm<F>::Word* __restrict__ scales, uint64_t nwords,
@@ -1116,10 +1134,19 @@ tenant_mxgemm_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint64_t v16,
   const uint64_t first = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
   for (uint64_t i = first; i < n16; i += stride) {
-    const uint64_t line = i / v16;
+    uint64_t at = i;  // the row-major index of the chunk that store i holds
+    if constexpr (kTiled) {
+      if (i >= rows_a * v16) {
+        const uint64_t j = i - rows_a * v16, unit = j / 256, steps = v16 / kGemmRowVecs;
+        const uint32_t p = static_cast<uint32_t>(j % 256) / 64, l = static_cast<uint32_t>(j % 64);
+        at = (rows_a + 32 * (unit / steps) + (l & 31u)) * v16 + kGemmRowVecs * (unit % steps) +
+             decode_chunk<F>(p, l >> 5);
+      }
+    }
+    const uint64_t line = at / v16;
     const bool is_b = line >= rows_a;
     const uint32_t row = static_cast<uint32_t>((is_b ? line - rows_a : line) % kGemmRowPeriod);
-    const uint32_t k0 = static_cast<uint32_t>((i % v16) * (4 * kPerDword) % kGemmKPeriod);
+    const uint32_t k0 = static_cast<uint32_t>((at % v16) * (4 * kPerDword) % kGemmKPeriod);
     int4v v;
 #pragma unroll
     for (uint32_t d = 0; d < 4; ++d) {
@@ -1652,6 +1679,8 @@ tenant_gemm_direct_kernel(const int4v* __restrict__ a, const int4v* __restrict__
 constexpr int kDecodeRows = 32;       // rows of A: the tokens of one decode step
 constexpr int kDecodeDefaultK = 8192;
 constexpr uint64_t kDecodeMaxN = 1 << 20;
+// Tiled weights: a wave's 32 rows x one step of 128 bytes, stored together.
+constexpr uint32_t kDecodeUnitBytes = 32 * kGemmRowVecs * 16;
 // A default launch lasts about as long as the gemm kinds' default launches
 // (profiles/decode_cotenancy_results.md).
 constexpr int kDecodeDefaultPasses[kMfmaForms] = {0, 0, 48, 48};
@@ -1673,13 +1702,6 @@ constexpr int kDecodeWaves = GPUPROBE_DECODE_WAVES;
 // (profiles/decode_cotenancy_results.md).
 static_assert(kDecodeDistance >= 2 && kDecodeDistance <= 8, "register sets of a wave");
 static_assert(kDecodeWaves >= 1 && kDecodeWaves <= 8, "waves per SIMD");
-
-// Which 16-byte chunk (0..7) of a row's 128-byte step lane half h holds in
-// piece p (0..3) of its registers; see the kernel.
-template <int F>
-__device__ constexpr uint32_t decode_chunk(uint32_t p, uint32_t h) {
-  return F == kMxfp8 ? 2 * p + h : 4 * h + p;
-}
 
 // One step's loads of a lane, as they come from global memory: the scale
 // words of its weight row and of its row of A, its chunk of A's slab and the
@@ -1752,6 +1774,20 @@ __device__ inline f32x16 decode_mfma(const int4v (&a)[4], const int4v (&w)[4], f
 // lane's offset is (32 j + r) x row bytes + 16 x chunk(0, h), the piece an
 // immediate, the step (128 x step) the shared offset.
 //
+// Weights, kTiled (weights = "tiled"): the same elements, W's 16-byte chunks
+// stored once in the order the waves consume them (the fill, kTiled): a unit
+// is a wave's 32 rows x one step, 4 KiB (kDecodeUnitBytes), units
+// row-block-major and then by step, and inside a unit [piece p][lane r + 32
+// h] is chunk decode_chunk<F>(p, h) of row 32 block + r, what that lane holds
+// as piece p either way. The same loads into the same registers on the same
+// descriptor (a tile's 128 rows are still one contiguous piece of 128 x row
+// bytes), at other offsets: the lane's is wave x steps x 4 KiB + 16 x lane,
+// the piece an immediate of 1 KiB x p, the step (4 KiB x step) the shared
+// offset. One wave instruction reads 1 KiB of consecutive addresses, 8 whole
+// lines, where row-major W has it touch 32 lines, and a wave's whole K is
+// one run of steps x 4 KiB. A, the scale words, the pipeline, the waits and
+// the result are the same code.
+//
 // Scales: global memory -> registers as in tenant_mxgemm_kernel, one word per
 // lane, step and operand (lanes r and r + 32 the same one), step-major so
 // that a wave's 32 rows are 128 or 256 contiguous bytes. The lane supplies
@@ -1809,7 +1845,12 @@ __device__ inline f32x16 decode_mfma(const int4v (&a)[4], const int4v (&w)[4], f
 //
 // Bounds. N and K are multiples of the tile and of the step. W: (32 j + r) x
 // row bytes + 16 x chunk + 128 x step + 15 with 32 j + r < 128, chunk < 8 and
-// step < steps is below 128 x row bytes, the window. A: the same with r < 32
+// step < steps is below 128 x row bytes, the window. Tiled W: j x steps x
+// 4096 + 16 x lane + 1024 x p + 4096 x step + 15 with j < 4, lane < 64, p < 4
+// and step < steps is at most j x steps x 4096 + 4096 (steps - 1) + 4095,
+// below (j + 1) x steps x 4096 <= 4 x steps x 4096 = 128 x row bytes, the same
+// window; past the last step bit 31 puts it outside, as for rows (the offset
+// stays below 2^31 + 2^22). A: the same as rows with r < 32
 // in a window of 32 rows. W's scale words: window from the tile's first word
 // to its last of the last step, ((steps - 1) N + 128) words, offset step x N +
 // 32 j + r; A's: steps x 32 words, offset 32 step + r. Every window is below
@@ -1829,16 +1870,30 @@ __device__ inline f32x16 decode_mfma(const int4v (&a)[4], const int4v (&w)[4], f
 // and mxfp4: 89 and 94 VGPRs (16 of accumulator, 2 x 22 or 24 of loads in
 // flight, 16 of A's fragments), no AGPRs, 45 and 49 SGPRs, no scratch and no
 // spills, 10240 bytes of LDS and an occupancy of 5 waves per SIMD, by
-// registers. Every kernel that was here before reports what it did.
+// registers. Every kernel that was here before reports what it did. The
+// tiled instantiations report 89 and 94 VGPRs, no AGPRs, 46 and 49 SGPRs, no
+// scratch and no spills, 10240 bytes of LDS and 5 waves per SIMD, and their
+// assembly has the waits of the row-major ones: vmcnt(11) for the scale
+// words, vmcnt(12) (mxfp8) or vmcnt(13) (mxfp4) in front of each MFMA,
+// vmcnt(13) in front of the slab write, no vmcnt(0) in the loop, the pieces
+// at offset:1024, 2048 and 3072. The row-major instantiations keep their
+// instructions, 427 and 444, one for one.
 //
 // On the card (profiles/decode_cotenancy_results.md) the default window
 // streams its weights at 5.2 (mxfp8) and 4.6 TB/s (mxfp4) where the stream
 // tenant reads 6.5-6.8, at an unlowered clock of 2.39 GHz, and on half the
 // CUs at 0.56 of that where the streamer keeps 6.1; neither the distance nor
 // the waves move it. So the limit is in the CUs, not HBM; a load instruction
-// touches 32 lines of 128 bytes, one per row, for 1 KiB, but which unit it
-// is was not measured.
-template <int F>
+// touches 32 lines of 128 bytes, one per row, for 1 KiB. That was the cause
+// (profiles/decode_tiled_cotenancy_results.md): on tiled weights, alternating
+// with row-major ones in fresh processes beside a streamer at 7.06 TB/s, the
+// default window streams 5.69 (mxfp8) and 5.67 TB/s (mxfp4) against 5.17 and
+// 4.59, and on half the CUs 4.66 and 4.27 against 2.92 and 2.54 where the
+// streamer reads 6.19. Four steps at three waves and eight at two, on tiled
+// weights, stayed within 1 % of two at five on the whole card and fell 1 to 7
+// % behind on half of it, so one distance and one occupancy serve both
+// layouts.
+template <int F, bool kTiled>
 __global__ void __launch_bounds__(kBlock, kDecodeWaves)
 tenant_decode_kernel(const int4v* __restrict__ a, const int4v* __restrict__ w,
                      const typename MxGemm<F>::Word* __restrict__ sa,
@@ -1848,7 +1903,11 @@ tenant_decode_kernel(const int4v* __restrict__ a, const int4v* __restrict__ w,
                      unsigned long long* __restrict__ clk) {
   using G = MxGemm<F>;
   constexpr int D = kDecodeDistance;
-  constexpr uint32_t kPiece = 16 * (decode_chunk<F>(1, 0) - decode_chunk<F>(0, 0));
+  // From one weight piece of a lane to its next, and from one step to the
+  // next: within the row, or through the row block's units.
+  constexpr uint32_t kPiece =
+      kTiled ? kDecodeUnitBytes / 4 : 16 * (decode_chunk<F>(1, 0) - decode_chunk<F>(0, 0));
+  constexpr uint32_t kStepBytes = kTiled ? kDecodeUnitBytes : kGemmRowVecs * 16;
   __shared__ int4v slab[2][kBlock];  // [buffer][plane x 64 + lane]
   __shared__ unsigned long long sums[kBlock];
   const uint32_t lane = threadIdx.x & 63u;
@@ -1857,7 +1916,8 @@ tenant_decode_kernel(const int4v* __restrict__ a, const int4v* __restrict__ w,
   const uint32_t tile = blockIdx.x % tiles;
   const uint32_t n_rows = tiles * kGemmTile;
   const uint32_t row_bytes = steps * (kGemmRowVecs * 16);
-  const uint32_t w_at = (32 * wave + r) * row_bytes + 16 * decode_chunk<F>(0, h);
+  const uint32_t w_at = kTiled ? wave * steps * kDecodeUnitBytes + 16 * lane
+                               : (32 * wave + r) * row_bytes + 16 * decode_chunk<F>(0, h);
   const uint32_t a_at = r * row_bytes + 16 * decode_chunk<F>(wave, h);
   const uint32_t sw_at = (32 * wave + r) * G::kWordBytes, sa_at = r * G::kWordBytes;
   const auto rw = buffer_window(w + static_cast<uint64_t>(tile) * kGemmTile * (row_bytes / 16),
@@ -1888,7 +1948,7 @@ tenant_decode_kernel(const int4v* __restrict__ a, const int4v* __restrict__ w,
       __attribute__((always_inline)) {
     const uint32_t outside = at_step < steps ? 0u : kBufferOutside;
     f.w[pc] = __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(
-        rw, (w_at | outside) + kPiece * pc, at_step * (kGemmRowVecs * 16), 0));
+        rw, (w_at | outside) + kPiece * pc, at_step * kStepBytes, 0));
     pin();
   };
   f32x16 acc;
@@ -2074,6 +2134,7 @@ struct TenantResult {
   bool lds = false;  // mfma only: operands re-read from LDS
   uint64_t lds_bytes = 0, lds_bytes_per_launch = 0;  // mfma from LDS only
   bool direct = false;  // gemm only: slabs loaded straight to LDS; sets lds_bytes too
+  bool tiled = false;   // decode only: W stored in the order the waves consume it
   MaskWords applied;
   double tick_hz = 0.0;
   int workgroups = 0;
@@ -2113,12 +2174,13 @@ void plan_gemm_grid(TenantResult& r, int tiles, int passes, int default_passes) 
 // process started under ROC_GLOBAL_CU_MASK the runtime reports only that mask's
 // CUs, so there the grid is 32 x its own CUs; every rate is over the work launched.)
 TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int passes,
-                         int form, bool lds, bool direct) {
+                         int form, bool lds, bool direct, bool tiled) {
   TenantResult r;
   r.kind = kind;
   r.form = is_mxgemm(kind) ? kind_info(kind).form : form;
   r.lds = lds;
   r.direct = direct;
+  r.tiled = tiled;
   r.workgroups = kind_info(kind).groups_per_cu * cus;
   const double lanes = static_cast<double>(r.workgroups) * kBlock;
   const uint64_t waves = static_cast<uint64_t>(r.workgroups) * kWavesPerGroup;
@@ -2308,8 +2370,9 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
         case Kind::kDecodeMxfp8:
         case Kind::kDecodeMxfp4:
           with_mx_form(r.form, [&](auto form) {
-            mx_go(form, tenant_decode_kernel<decltype(form)::value>, r.tiles, rec,
-                  clks.at(2 * slot));
+            constexpr int F = decltype(form)::value;
+            mx_go(form, r.tiled ? tenant_decode_kernel<F, true> : tenant_decode_kernel<F, false>,
+                  r.tiles, rec, clks.at(2 * slot));
           });
           break;
       }
@@ -2333,7 +2396,9 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
       case Kind::kDecodeMxfp4:
         with_mx_form(r.form, [&](auto form) {
           constexpr int F = decltype(form)::value;
-          go(dim3(kGroupsPerCu * cus), tenant_mxgemm_fill_kernel<F>, buf.as<int4v>(), n16,
+          go(dim3(kGroupsPerCu * cus),
+             r.tiled ? tenant_mxgemm_fill_kernel<F, true> : tenant_mxgemm_fill_kernel<F>,
+             buf.as<int4v>(), n16,
              static_cast<uint64_t>(r.iters) * kGemmRowVecs,
              scales.as<typename MxGemm<F>::Word>(), (r.m + r.n) * r.iters, r.m, r.n,
              mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
@@ -2411,13 +2476,13 @@ void summarise(TenantResult& r) {
 
 TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int launches,
                         int iters, uint64_t bytes, int passes, uint64_t seed, int form,
-                        bool lds, bool direct) {
+                        bool lds, bool direct, bool tiled) {
   require_device(device);
   const int cus = gpuprobe::device_cus(device);
   const MaskWords mask =
       raw_mask.empty() ? MaskWords{} : gpuprobe::fit_mask(raw_mask, cus);
   launches = std::min(std::max(launches, 1), kMaxLaunches);
-  TenantResult r = plan_tenant(kind, cus, iters, bytes, passes, form, lds, direct);
+  TenantResult r = plan_tenant(kind, cus, iters, bytes, passes, form, lds, direct, tiled);
   if (kind_info(kind).reads) {
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
@@ -2444,7 +2509,7 @@ void register_cotenant(py::module_& m) {
       "cu_tenant_run",
       [](int device, py::object mask, const std::string& kind, int launches, int iters,
          uint64_t bytes, int passes, uint64_t seed, const std::string& form,
-         const std::string& operands, const std::string& loads) {
+         const std::string& operands, const std::string& loads, const std::string& weights) {
         const MaskWords words = gpuprobe::mask_from_python(mask);
         int k = 0;
         while (k < kKinds && kind != kKindTable[k].name) ++k;
@@ -2481,11 +2546,19 @@ void register_cotenant(py::module_& m) {
           throw py::value_error(
               "cu_tenant_run: loads \"direct\" needs kind \"gemm\"; of the loads "
               "\"registers\" and \"direct\" every other kind takes only \"registers\"");
+        if (weights != "rows" && weights != "tiled")
+          throw py::value_error("cu_tenant_run: weights must be \"rows\" or \"tiled\"");
+        const bool tiled = weights == "tiled";
+        if (tiled && kKindTable[k].family != Family::kDecode)
+          throw py::value_error(
+              "cu_tenant_run: weights \"tiled\" needs kind \"decode-mxfp8\" or "
+              "\"decode-mxfp4\"; of the weights \"rows\" and \"tiled\" every other kind takes "
+              "only \"rows\"");
         TenantResult r;
         {
           py::gil_scoped_release release;
           r = run_tenant(device, words, static_cast<Kind>(k), launches, iters, bytes,
-                         passes, seed, f, lds, direct);
+                         passes, seed, f, lds, direct, tiled);
         }
         py::dict d;
         if (r.skipped) {
@@ -2546,6 +2619,7 @@ void register_cotenant(py::module_& m) {
               d["stages"] = kGemmDirectStages;
               d["lds_bytes"] = r.lds_bytes;
             }
+            if (r.tiled) d["weights"] = weights;
             break;
         }
         if (clocks) last["clock_ghz"] = r.clock_ghz;
@@ -2574,6 +2648,7 @@ void register_cotenant(py::module_& m) {
       py::arg("launches") = 8, py::arg("iters") = 0, py::arg("bytes") = 0,
       py::arg("passes") = 0, py::arg("seed") = 1, py::arg("form") = "bf16",
       py::arg("operands") = "registers", py::arg("loads") = "registers",
+      py::arg("weights") = "rows",
       "One tenant's workload, stamped with the card's wall clock. `mask` as in "
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
@@ -2847,13 +2922,29 @@ void register_cotenant(py::module_& m) {
       "seed, form=), load_bytes_per_launch = tiles * passes * iters * (16384 "
       "+ 4096 + 256 x 4 or 8), work_per_launch = 2 x 32 N K passes, rates in "
       "GFLOP/s and the clocks. The free-memory refusal counts A, W and the "
-      "scale words. Neither takes a form, operands or loads.\n\n"
+      "scale words. Neither takes a form, operands or loads. `weights` "
+      "(\"rows\", the default, or \"tiled\"; anything else raises ValueError, "
+      "as does \"tiled\" on any other kind) says how W lies in memory. "
+      "\"rows\" is row-major: every lane of a weight load sits on its own row, "
+      "so one wave instruction touches 32 lines of 128 bytes for 1 KiB. "
+      "\"tiled\" is the layout production decode GEMMs shuffle their weights "
+      "into once, offline: the same elements under the same scales, the "
+      "16-byte chunks in the order a wave consumes them. A unit is 32 rows x "
+      "one step, 4 KiB, units row-block-major and then by step, inside a unit "
+      "[piece p][lane r + 32 h] = the chunk that lane holds as piece p of row "
+      "32 block + r. A wave instruction then reads 1 KiB of consecutive "
+      "addresses, 8 whole lines, and a wave's whole K is one run of iters x 4 "
+      "KiB; the lane's offset is 16 x lane, the piece an immediate of 1 KiB, "
+      "the step 4 KiB. The fill writes W in that order, A and the scale words "
+      "stay as they are, the product and so the checksum are the same, and "
+      "so is every shape and byte key; the result adds weights = \"tiled\" "
+      "after load_bytes_per_launch.\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
       "{kind, [form,] applied_mask, tick_hz, workgroups, iters | [m, n, k,] bytes, "
       "[scale_bytes,] passes, "
-      "checksum, [load_bytes_per_launch, [loads, stages, lds_bytes,]] "
+      "checksum, [load_bytes_per_launch, [loads, stages, lds_bytes,] [weights,]] "
       "[operands, lds_bytes, lds_bytes_per_launch,] "
       "[bytes_per_cu,] work_per_launch: flops, bytes or hops, launches: [{t0, t1, "
       "seconds: (t1 - t0) "
