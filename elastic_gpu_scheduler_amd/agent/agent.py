@@ -489,6 +489,14 @@ class NodeAgent:
         same matrix shuffled once into the order the waves consume it, as
         production decode GEMMs keep their weights, so that every load
         instruction reads whole lines; their entries then add "weights".
+        pairs=cotenancy.attention_pairs() brings in the other prefill kernel,
+        a causal flash-attention forward pass in bf16 (window: iters =
+        sequence length / 128, bytes of Q + K + V, passes), beside itself,
+        the streamer, the gemm kind and decode-mxfp4, both ways round. It has
+        no checksum: the probe holds sampled rows of its output against an
+        fp64 reference, and an error above cotenancy.ATTENTION_TOLERANCE makes
+        the report not ok ("bad-output"). Its entries carry the clock and its
+        split, and it takes none of form, operands, loads and weights.
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched

@@ -84,7 +84,23 @@ consumes them (units of 32 rows x one step, 4 KiB), where it reads 8 whole
 lines and a wave's K is one contiguous run: what production decode GEMMs on
 this chip do with their weights offline. The elements, the scales, the
 product and so the checksum are the same. TENANT_KINDS stays the kinds
-before them; CO_KINDS is every kind a child can be started as.
+before them; CO_KINDS is those and the decode kinds.
+
+The last kind, "attention" (ATTENTION_KINDS, WORKLOAD_KINDS,
+attention_pairs()), is the other kernel a transformer tenant spends its
+prefill in: a causal flash-attention forward pass in bf16, head dimension
+128. It keeps the matrix pipe and the transcendental unit (v_exp_f32) busy
+in one wave, re-reads a head's K and V out of L2 and the Infinity Cache once
+per query tile, and its workgroups are not equally long, so a launch has a
+tail. Its window is `iters` (the sequence length in units of 128 rows, 0:
+8192 rows), `bytes` (Q plus K plus V, 0: 64 heads) and `passes` (whole
+forward passes per launch); attention_shape() states the shape and
+attention_operands() the data. Its output is no integer, so it has no
+checksum: the probe recomputes 256 sampled rows in fp64 after the timed
+launches and reports max_error, which a report holds against
+ATTENTION_TOLERANCE. It reports the clock it saw and a pair splits its ratio
+as for the GEMM kinds; it takes neither form nor operands nor loads nor
+weights. WORKLOAD_KINDS is every kind a child can be started as.
 
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
@@ -159,6 +175,62 @@ def decode_pairs(kind: str) -> Tuple[Tuple[str, str], ...]:
     if kind not in DECODE_KINDS:
         raise ValueError(f"not a decode kind: {kind!r}")
     return ((kind, kind), (kind, "stream"), ("stream", kind), (kind, "gemm"), ("gemm", kind))
+
+
+# The kind that is a causal flash-attention forward pass, and every kind a
+# child can be started as.
+ATTENTION_KINDS = ("attention",)
+WORKLOAD_KINDS = CO_KINDS + ATTENTION_KINDS
+ATTENTION_HEAD_DIM = 128
+# What |O - float64 reference| may be for an attention tenant's bf16 output:
+# derived, not measured. With |v| <= 15/16 the rounding of P to bf16 moves an
+# output by at most 2^-8 * 15/16 (truncation) or 2^-9 * 15/16 (nearest); the
+# bf16 store of O adds at most another 2^-9 * 15/16; f32 accumulation over seq
+# <= 32768 terms adds at most seq * 2^-24; and the exp2 argument carries at
+# most 230 * 2^-23 of relative error into p. All of that is below 2^-7. A numpy
+# emulation of the kernel's arithmetic (f32 exp2, P to bf16, f32 accumulate,
+# bf16 store) at seq 128, 384 and 1024 stays within 0.0031 with truncation and
+# 0.0024 with round-to-nearest, while dropping one K/V tile moves 99-100 % of
+# the rows behind it beyond 2^-7 and a mask one key too wide 10-41 % of all
+# rows.
+ATTENTION_TOLERANCE = 2 ** -7
+
+
+def attention_pairs() -> Tuple[Tuple[str, str], ...]:
+    """The pairs that say what a neighbour does to an attention tenant and
+    what it does to them: another such tenant, the streamer, the prefill bf16
+    GEMM and the decode-mxfp4 tenant (the prefill/decode mix of a serving
+    node), both ways round each."""
+    others = ("stream", "gemm", "decode-mxfp4")
+    return (("attention", "attention"),) + tuple(
+        pair for kind in others for pair in (("attention", kind), (kind, "attention")))
+
+
+def attention_shape(bytes: int = 0, iters: int = 0) -> Tuple[int, int, int]:
+    """(heads, seq, 128) of the forward pass an attention tenant runs for the
+    window keys `bytes` and `iters`, the probe's rule stated on its own: seq =
+    128 * iters (0: 64, seq 8192; clamped to 1 .. 256), and heads = bytes //
+    (768 * seq), a row of Q, K and V being 768 bytes of bf16 (0: 64 heads),
+    clamped to 1 .. 1024."""
+    seq = 128 * (min(int(iters), 256) if int(iters) > 0 else 64)
+    heads = int(bytes) // (768 * seq) if int(bytes) else 64
+    return min(max(heads, 1), 1024), seq, ATTENTION_HEAD_DIM
+
+
+def attention_operands(seed: int, head: int, seq: int
+                       ) -> Tuple[List[List[float]], List[List[float]], List[List[float]]]:
+    """Q, K and V ([seq][128] each) of `head` of an attention tenant, the
+    probe's data rule stated on its own: key = mix32(mix32(seed32 ^ 0x4154544E)
+    ^ which * 0x9E3779B1 ^ head) with which = 0, 1, 2, and the element at
+    [row][d] is (mix32(key ^ (row << 7 | d)) % 31 - 15) / 8, / 4 or / 16, all
+    exact in bf16."""
+    base = _mix32((int(seed) & _M32) ^ 0x4154544E)
+    out = []
+    for which, scale in enumerate((8.0, 4.0, 16.0)):
+        key = _mix32(base ^ (which * 0x9E3779B1 & _M32) ^ int(head))
+        out.append([[(_mix32(key ^ (row << 7 | d)) % 31 - 15) / scale
+                     for d in range(ATTENTION_HEAD_DIM)] for row in range(int(seq))])
+    return out[0], out[1], out[2]
 
 
 # What may differ from tenant to tenant, or from kind to kind, within one call.
@@ -548,7 +620,7 @@ def _child_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="cotenancy", description=__doc__)
     p.add_argument("--child", action="store_true", required=True)
     p.add_argument("--device", type=int, default=0)
-    p.add_argument("--kind", choices=CO_KINDS, default="fma")
+    p.add_argument("--kind", choices=WORKLOAD_KINDS, default="fma")
     p.add_argument("--launches", type=int, default=8)
     p.add_argument("--iters", type=int, default=0)
     p.add_argument("--bytes", type=int, default=0)
@@ -687,8 +759,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
     "fma" | "stream" | "cache" | "chase" | "mfma" | "gemm" | "gemm-mxfp8" |
-    "gemm-mxfp4" | "decode-mxfp8" | "decode-mxfp4"} and may carry its
-    own "launches", "iters",
+    "gemm-mxfp4" | "decode-mxfp8" | "decode-mxfp4" | "attention"} and may
+    carry its own "launches", "iters",
     "bytes" and "passes" in place of the call-wide ones; `kinds`, when given,
     names the kinds instead. Every child warms up and says READY; only then
     are all told GO. Returns {"ok": True, "tenants": [the children's
@@ -723,7 +795,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     "weights" on a tenant of any other kind raises ValueError before
     anything is started, the call-wide value leaves the other kinds as they
     are, and a child is given --weights, after --loads, only when one was
-    named for it.
+    named for it. An attention tenant takes none of the four: its child is
+    started with its window alone.
 
     Each child has `timeout` seconds from its start. The first child that
     times out, exits non-zero or prints no TENANT line ends the run: the
@@ -749,7 +822,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     try:
         for i, tenant in enumerate(tenants):
             kind = kinds[i] if kinds is not None else tenant["kind"]
-            if kind not in CO_KINDS:
+            if kind not in WORKLOAD_KINDS:
                 raise ValueError(f"unknown tenant kind {kind!r}")
             env = dict(os.environ)
             env[ENV_CU_MASK] = mask_hex(int(tenant["mask"]))
@@ -821,7 +894,8 @@ def _balanced(launches: int, seconds: Sequence[float]) -> List[int]:
 # What a report knows of each kind. First the keys of a child's result that a
 # solo entry adds; a kind that adds clock_ghz gets the clock split in a pair.
 _SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",), "gemm": ("clock_ghz",),
-              **{kind: ("clock_ghz",) for kind in MXGEMM_KINDS + DECODE_KINDS}}
+              **{kind: ("clock_ghz",) for kind in MXGEMM_KINDS + DECODE_KINDS},
+              "attention": ("clock_ghz",)}
 
 
 def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
@@ -923,6 +997,18 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     and cycle_ratio what the shared memory path took. It takes neither
     `form` nor `operands` nor `loads`.
 
+    An attention tenant (pairs=attention_pairs()) is a causal
+    flash-attention forward pass in bf16: `iters` is the sequence length in
+    units of 128 rows, `bytes` Q plus K plus V, `passes` whole forward passes
+    per launch, see attention_shape(). Its rates are GFLOP/s over the
+    unmasked half of Q K^T and P V. It has no checksum; its result carries
+    max_error, the largest difference between its output and the probe's
+    fp64 reference over 256 sampled rows, and a max_error above
+    ATTENTION_TOLERANCE makes the report not ok with reason "bad-output",
+    the figures kept as for "bad-checksum". Its entries carry the clock and
+    its split as a gemm tenant's do. It takes none of `form`, `operands`,
+    `loads` and `weights`.
+
     `form` (one of MFMA_FORMS, anything else raises ValueError) is the
     instruction the mfma tenants issue, alone and in every pair; a tenant
     ({"mask": int, "form": str}) may name its own instead, for a bf16 tenant
@@ -971,11 +1057,11 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     if len(tenants) != 2:
         raise ValueError("isolation_report takes two tenants")
     for pair in pairs:
-        if len(pair) != 2 or any(k not in CO_KINDS for k in pair):
+        if len(pair) != 2 or any(k not in WORKLOAD_KINDS for k in pair):
             raise ValueError(f"not a pair of tenant kinds: {pair!r}")
     windows = {kind: dict(w) for kind, w in (windows or {}).items()}
     for kind, w in windows.items():
-        if kind not in CO_KINDS or any(k not in WINDOW_KEYS for k in w):
+        if kind not in WORKLOAD_KINDS or any(k not in WINDOW_KEYS for k in w):
             raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
     # Per option and tenant, what the tenant is started with as a tenant of
     # the option's kind.
@@ -1010,10 +1096,15 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
         expected = _expected(result, seed, pattern, **options(i, result["kind"]))
         if expected is not None and int(result["checksum"]) != expected:
             return "bad-checksum"
+        # An attention tenant has no checksum: the probe's own fp64 reference
+        # says how far its output is off (a not-a-number is not within).
+        if result["kind"] in ATTENTION_KINDS and not (
+                result["max_error"] <= ATTENTION_TOLERANCE):
+            return "bad-output"
         return None
 
     for i, tenant in enumerate(tenants):
-        for kind in CO_KINDS:
+        for kind in WORKLOAD_KINDS:
             if not any(pair[i] == kind for pair in pairs):
                 continue
             run = run_pair(card, [{"mask": tenant["mask"], "kind": kind,

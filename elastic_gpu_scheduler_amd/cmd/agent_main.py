@@ -35,6 +35,8 @@ block-scaled GEMM, 32 token rows against a weight matrix streamed from
 memory, beside itself, the streamer and the prefill GEMM;
 --co-tenancy-decode-weights tiled gives it its weights pre-shuffled into the
 order its waves consume them, as production decode GEMMs keep theirs.
+--co-tenancy-attention runs a causal flash-attention forward pass, the other
+prefill kernel, beside itself, the streamer, the GEMM and the decode tenant.
 """
 from __future__ import annotations
 
@@ -229,6 +231,20 @@ def build_parser() -> argparse.ArgumentParser:
                         "so that every load instruction reads whole lines and "
                         "a wave's K is one contiguous run, as production "
                         "decode GEMMs on gfx950 keep their weights")
+    p.add_argument("--co-tenancy-attention", action="store_true",
+                   help="with --co-tenancy: instead of the FMA and stream "
+                        "pairs, run a tenant that computes a causal "
+                        "flash-attention forward pass in bf16 (64 heads of "
+                        "8192 rows, head dimension 128: MFMAs, exp2 and LDS "
+                        "in one wave, K and V re-read from the caches) next "
+                        "to another such tenant, next to the 1 GiB streamer, "
+                        "next to the prefill bf16 GEMM and next to the "
+                        "decode-mxfp4 tenant (both ways round each), and "
+                        "print one report per card, each ratio split into "
+                        "clock_ratio and cycle_ratio; not together with "
+                        "--co-tenancy-cache, --co-tenancy-chase, "
+                        "--co-tenancy-mfma, --co-tenancy-gemm or "
+                        "--co-tenancy-decode")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -272,7 +288,10 @@ def main(argv=None) -> int:
             ("--co-tenancy-decode", "--co-tenancy",
              ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma",
               "--co-tenancy-gemm")),
-            ("--co-tenancy-decode-weights", "--co-tenancy-decode", ())):
+            ("--co-tenancy-decode-weights", "--co-tenancy-decode", ()),
+            ("--co-tenancy-attention", "--co-tenancy",
+             ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma",
+              "--co-tenancy-gemm", "--co-tenancy-decode"))):
         if not given(flag):
             continue
         if not given(needs):
@@ -285,13 +304,15 @@ def main(argv=None) -> int:
 
     if args.co_tenancy is not None:
         from elastic_gpu_scheduler_amd.agent.cotenancy import (
-            CACHE_PAIRS, CHASE_PAIRS, GEMM_PAIRS, MFMA_PAIRS, cache_passes, decode_pairs,
-            mxgemm_pairs)
+            CACHE_PAIRS, CHASE_PAIRS, GEMM_PAIRS, MFMA_PAIRS, attention_pairs, cache_passes,
+            decode_pairs, mxgemm_pairs)
 
         # What every report of the run is asked for and, where a flag names
         # several forms or sizes, what each of them adds, by its label.
         common, each = {}, None
-        if args.co_tenancy_decode is not None:
+        if args.co_tenancy_attention:
+            common = {"pairs": attention_pairs()}
+        elif args.co_tenancy_decode is not None:
             each = {form: {"pairs": decode_pairs("decode-" + form)}
                     for form in args.co_tenancy_decode}
             if args.co_tenancy_decode_weights is not None:

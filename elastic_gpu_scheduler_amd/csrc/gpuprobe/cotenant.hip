@@ -10,7 +10,8 @@
 //     or a whole GEMM fed from memory through LDS, bf16 ("gemm") or
 //     block-scaled ("gemm-mxfp8", "gemm-mxfp4"), or the decode shape of the
 //     latter, 32 rows against weights streamed from memory straight into
-//     registers ("decode-mxfp8", "decode-mxfp4"),
+//     registers ("decode-mxfp8", "decode-mxfp4"), or a causal flash-attention
+//     forward pass in bf16 ("attention"),
 //     each launch stamped with the device's constant-rate wall clock. The
 //     clock is the card's, not the
 //     process's, so two separate processes can lay their launches side by
@@ -28,6 +29,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -2025,20 +2027,454 @@ tenant_decode_kernel(const int4v* __restrict__ a, const int4v* __restrict__ w,
   clocked_end(rec, clk, c0, t0);
 }
 
+// ---- attention ---------------------------------------------------------------
+
+constexpr int kAttnDim = 128;    // head dimension: a row of Q, K, V or O is 256 bytes
+constexpr int kAttnRows = 128;   // query rows per workgroup, 32 per wave
+constexpr int kAttnKeys = 64;    // keys per K/V tile
+constexpr int kAttnRowVecs = kAttnDim * 2 / 16;          // 16-byte chunks per row: 16
+constexpr int kAttnTileVecs = kAttnKeys * kAttnRowVecs;  // one tile of K or V: 16 KiB
+constexpr int kAttnLoads = kAttnTileVecs / kBlock;       // loads per lane, operand and tile: 4
+constexpr uint32_t kAttnKeySalt = 0x4154544Eu;
+constexpr int kAttnDefaultIters = 64, kAttnMaxIters = 256;  // sequence length / 128
+constexpr uint64_t kAttnDefaultHeads = 64, kAttnMaxHeads = 1024;
+// A default launch on a whole card lasts about as long as gemm's
+// (profiles/attention_cotenancy_results.md).
+constexpr int kAttnDefaultPasses = 8;
+constexpr int kAttnSamples = 256;  // rows the reference kernel recomputes
+constexpr uint64_t kAttnMaxOutput = 64 * kMiB;  // attention_output: the most it returns
+// log2(e) / sqrt(128): exp((s - m) / sqrt(128)) = exp2((s - m) * kAttnScale).
+constexpr float kAttnScale = 1.4426950408889634f * 0.08838834764831845f;
+
+using short4v = __attribute__((ext_vector_type(4))) short;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+
+// A value that bf16 holds exactly, as its bits: the float's upper half.
+__device__ inline short exact_bf16_bits(float v) {
+  return static_cast<short>(__float_as_uint(v) >> 16);
+}
+
+// The operands of an attention tenant: `buf` is Q, then K, then V, each
+// [head][row][128] bf16. key = mix32(seed_key ^ which * 0x9E3779B1 ^ head) with
+// which = 0, 1, 2 and seed_key = mix32(seed32 ^ 0x4154544E); the element at
+// [row][d] is (mix32(key ^ (row << 7 | d)) % 31 - 15) / 8, / 4 or / 16: at most
+// four significant bits under a power of two, exact in bf16. One 16-byte store
+// of eight elements per step, grid-stride; n16 = 3 * heads * seq * 16 counts
+// the stores. All indices are 64-bit and below n16; row < 2^15, so row << 7 | d
+// is below 2^22.
+__global__ void __launch_bounds__(kBlock)
+tenant_attention_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint32_t heads,
+                             uint32_t seq, uint32_t seed_key) {
+  uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+  const uint64_t per_head = static_cast<uint64_t>(seq) * kAttnRowVecs;
+  const uint64_t per_operand = per_head * heads;
+  for (; i < n16; i += stride) {
+    const uint32_t which = static_cast<uint32_t>(i / per_operand);
+    const uint64_t at = i % per_operand;
+    const uint32_t head = static_cast<uint32_t>(at / per_head);
+    const uint32_t row = static_cast<uint32_t>(at % per_head / kAttnRowVecs);
+    const uint32_t d0 = static_cast<uint32_t>(at % kAttnRowVecs) * 8;
+    const uint32_t key = mix32(seed_key ^ (which * 0x9E3779B1u) ^ head);
+    const float scale = which == 0 ? 0.125f : which == 1 ? 0.25f : 0.0625f;
+    short8 v;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) {
+      const uint32_t hash = mix32(key ^ (row << 7 | (d0 + j)));
+      v[j] = exact_bf16_bits(static_cast<float>(static_cast<int>(hash % 31u) - 15) * scale);
+    }
+    buf[i] = __builtin_bit_cast(int4v, v);
+  }
+}
+
+// Where 16-byte chunk c (0..15, d = 8c .. 8c + 7) of row `row` of a K tile or
+// of a V tile lives, as the XOR key of its chunk position: a row's 256 bytes
+// are unpadded and span all 64 banks, so only the position decides the banks.
+//   K is read as MFMA A fragments with ds_read_b128, lane r on row base + r at
+//   one chunk per h: the key takes 16 values over 16 consecutive rows, and
+//   rows 0..7 differ in its upper three bits, so that 16 lanes of one h, or
+//   eight of h = 0 (chunk c) with eight of h = 1 (chunk c ^ 1), fall into 16
+//   different bank groups of 16 bytes (gemm_key's argument, for 16 chunks).
+//   V is read with ds_read_b64_tr_b16, 32 lanes on 4 consecutive rows (base a
+//   multiple of 4) x 4 consecutive chunks 4u .. 4u + 3: the key moves row
+//   (R & 3) by 4 (R & 3) chunks, so the 16 (row, chunk) pairs take all 16
+//   positions and the 32 8-byte reads all 64 banks.
+__device__ inline uint32_t attn_k_key(uint32_t row) {
+  return ((row & 7u) << 1) | ((row >> 3) & 1u);
+}
+__device__ inline uint32_t attn_v_key(uint32_t row) { return (row & 3u) << 2; }
+
+// One number across the lane pair (l, l + 32), which holds one query column:
+// v_permlane32_swap exchanges the upper half of its first operand with the
+// lower half of its second, so with both operands x the two results are, in
+// either half, the lane's own x and the other lane's.
+__device__ inline f32x2 attn_pair(float x) {
+  const auto both = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x),
+                                                     false, false);
+  return f32x2{__uint_as_float(both[0]), __uint_as_float(both[1])};
+}
+
+// A causal flash-attention forward pass in bf16: per head O = softmax(Q K^T /
+// sqrt(128), causal) V, row i attending to keys 0 .. i, head dimension 128, Q,
+// K, V and O row-major [head][row][128]. The grid is passes x heads x seq / 128
+// workgroups, every pass the same product into its own O.
+//
+// Work split. A workgroup owns 128 query rows of one head of one pass, wave j
+// rows 32 j .. 32 j + 31. Workgroup g of a pass takes query tile T - 1 - g /
+// heads of head g % heads, T = seq / 128: the longest tiles (most keys) start
+// first, so that what is left at the end of a launch are the short ones.
+// (Supposed, not measured: if consecutive workgroup ids go round the 8 XCDs,
+// as gemm_order takes them to, then with heads a multiple of 8 a head's
+// workgroups, heads apart in g, share one XCD and its L2 for K and V. No
+// counter was read to confirm it.)
+//
+// Scores. Per tile of 64 keys a wave computes S^T = K Q^T, 64 keys x 32
+// queries, as two 32 x 32 accumulators (keys 32 t ..) over d = 128 in eight
+// v_mfma_f32_32x32x16_bf16 each: A is K from LDS (lane r + 32 h: key 32 t + r,
+// chunk 2 s + h at sub-step s), B is Q, loaded once from memory into registers
+// in that same fragment layout (lane r + 32 h: query r, chunk 2 s + h). Lane r
+// + 32 h then holds in register i of accumulator t the score of query r and
+// key 32 t + (i & 3) + 8 (i >> 2) + 4 h: 32 keys of one query column. The
+// maximum of a column is an in-lane maximum and one exchange with lane r + 32
+// h ^ 32 (attn_pair); no LDS round trip.
+//
+// Softmax, online and in base 2: m is the running maximum of the raw scores
+// and l the running sum, both f32; a tile gives m' = max(m, tile), alpha =
+// exp2((m - m') c), p = exp2((s - m') c), c = log2(e) / sqrt(128), l = l alpha
+// + sum of p, O = O alpha + P V, all exponentials v_exp_f32. A lane sums only
+// its own 32 keys into l (alpha is the pair's), and the pair is added up once
+// at the end, where O is divided by l and stored as bf16. Key 0 is in every
+// row's first tile and never masked, so m is finite from the first tile on:
+// alpha is exp2(-inf) = 0 there, and a tile whose keys a row may not see at
+// all leaves m alone and gives p = exp2(-inf) = 0.
+//
+// Output. O^T = V^T P^T, 128 d x 32 queries as four accumulators (d 32 u ..),
+// 16 MFMAs per tile: sixteen keys a step, step (t, g) taking registers 8 g ..
+// 8 g + 7 of score accumulator t, rounded to bf16 (nearest even), as they are
+// as the B operand. Lane r + 32 h, slot e of that operand is key kappa = 32 t
+// + 16 g + 8 (e >> 2) + 4 h + (e & 3), not the 8 h + e the instruction counts
+// by; P is not moved, the A operand pairs it with V[kappa]: lane r' + 32 h,
+// slot e holds V[kappa][32 u + r']. Those come from the row-major V tile with
+// two ds_read_b64_tr_b16 per fragment: in a block of 16 lanes, lane i points
+// at the four elements 4 (i & 3) .. + 3 of row i >> 2 of a 4 x 16 block, and
+// receives column i of its four rows. Block b = lane >> 4 reads rows 32 t +
+// 16 g + 8 x + 4 h .., x = 0, 1 the half of the fragment, columns 32 u + 16
+// (b & 1) ...
+//
+// Data movement. K and V travel global memory -> LDS in tiles of 64 keys, 16
+// KiB each, with tenant_gemm_direct_kernel's 16-byte LDS-DMA load and its
+// discipline: LDS holds two pairs {K tile, V tile}, 64 KiB, two workgroups per
+// CU; step i issues the eight loads of tile i + 1 into the other pair,
+// computes from pair i & 1, waits for vmcnt(0) and crosses one barrier. The
+// pair overwritten in step i was last read in step i - 1, which every wave
+// left through its barrier after its MFMAs had consumed what it read. One
+// wave instruction fills 64 consecutive chunk positions, four whole rows:
+// wave w's instruction i fills rows 16 i + 4 w .. + 3, lane l on row R = 16 i
+// + 4 w + (l >> 4) at position l & 15, and fetches chunk (l & 15) ^ key(R)
+// of that row; neither key depends on i (attn_k_key: bits 0..3 of R are those
+// of 4 w + (l >> 4); attn_v_key: bits 0..1 are l >> 4).
+//
+// Masking. Tiles above the diagonal are never loaded: a workgroup on query
+// tile qt runs 2 (qt + 1) tiles, keys 0 .. 128 qt + 127. Only the last two can
+// hold a key beyond one of its rows; there, and only there, a score whose key
+// is beyond its query is set to -inf before the maximum.
+//
+// Barriers. The tile count is the workgroup's, from blockIdx alone: every wave
+// runs the same number of steps and reaches every barrier, a wave whose rows
+// see nothing of a tile included; the only branches inside a step are the
+// mask's, which holds no barrier and no load. No load has a branch around it:
+// the tile past the last is issued with bit 31 set in every lane's offset,
+// outside any window, reads nothing, and lands in a pair nobody reads again.
+//
+// Bounds. Buffer loads on a descriptor of the head's K or V, seq x 256 bytes
+// (at most 8 MiB): a lane's offset is (4 w + (l >> 4)) x 256 + 16 x chunk, the
+// shared one (64 tile + 16 i) x 256, together row x 256 + 16 chunk with row <
+// 64 (tile + 1) <= 128 (qt + 1) <= seq and chunk < 16. An LDS address handed
+// to a load is pair x 32 KiB + operand x 16 KiB + (16 i + 4 w) x 256 + 16 l +
+// 15 < 64 KiB, wave-uniform by construction. A fragment read is row < 64 and
+// position < 16 of a tile. Q and O rows are 128 qt + 32 j + r < seq of the
+// head, and the pass's O.
+//
+// Stamps and clocks are the gemm kinds' (clocked_end); Q's loads and the
+// first tile's are inside them.
+//
+// hipcc -O3 for gfx950 reports (-Rpass-analysis=kernel-resource-usage) 176
+// VGPRs, no AGPRs, 38 SGPRs, no scratch and no spills, 65536 bytes of LDS and
+// an occupancy of 2 waves per SIMD, by LDS and by registers alike. On the
+// card it spends 61.4-63.4 (whole card) and 61.2-61.5 (half) cycles per MFMA
+// and SIMD where the instruction takes 32, about 0.52 of the matrix pipe
+// (profiles/attention_cotenancy_results.md).
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"  // m0 is clobbered on purpose
+__global__ void __launch_bounds__(kBlock, 2)
+tenant_attention_kernel(const int4v* __restrict__ q, const int4v* __restrict__ k,
+                        const int4v* __restrict__ v, short4v* __restrict__ o, uint32_t heads,
+                        uint32_t qtiles, unsigned long long* __restrict__ rec,
+                        unsigned long long* __restrict__ clk) {
+  __shared__ int4v ring[2][2][kAttnTileVecs];  // [pair][K, V]
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = lane & 31u, h = lane >> 5;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+  const uint32_t per_pass = heads * qtiles;
+  const uint32_t pass = blockIdx.x / per_pass, in_pass = blockIdx.x % per_pass;
+  const uint32_t qt = qtiles - 1 - in_pass / heads, head = in_pass % heads;
+  const uint32_t seq = qtiles * kAttnRows;
+  const uint32_t tiles = 2 * (qt + 1);
+  const uint64_t head_vecs = static_cast<uint64_t>(seq) * kAttnRowVecs;
+  // What this lane loads: of rows 4 wave + (lane >> 4) + 16 i the chunk that
+  // belongs at position lane & 15.
+  const uint32_t land_row = 4 * wave + (lane >> 4);
+  const uint32_t load_k = land_row * 256 + 16 * ((lane & 15u) ^ attn_k_key(land_row));
+  const uint32_t load_v = land_row * 256 + 16 * ((lane & 15u) ^ attn_v_key(land_row));
+  const uint32_t land_at = 4 * wave * kAttnRowVecs;  // + 16 rows: + 256
+  const auto window = [&](const int4v* first) {
+    const uint64_t base = reinterpret_cast<uint64_t>(first);
+    return int4v{static_cast<int>(static_cast<uint32_t>(base)),
+                 static_cast<int>(static_cast<uint32_t>(base >> 32) & 0xFFFFu),
+                 static_cast<int>(seq * 256u), kBufferWord3};
+  };
+  const auto rk = window(k + head * head_vecs);
+  const auto rv = window(v + head * head_vecs);
+  // What this lane reads of a K tile: rows r + 32 t, chunk (2 s + h) ^ key; of
+  // a V tile, per d block u: row 4 h + (i >> 2) (+ 32 t + 16 g + 8 x), chunk 4 u
+  // + 2 (b & 1) + ((i >> 1) & 1) under the row's key 4 (i >> 2), bytes 8 (i & 1)
+  // .. + 7 of it, i = lane & 15 and b = lane >> 4.
+  const uint32_t read_k = r * kAttnRowVecs, read_key = attn_k_key(r);
+  const uint32_t i16 = lane & 15u;
+  uint32_t read_v[4];  // in bytes
+#pragma unroll
+  for (uint32_t u = 0; u < 4; ++u)
+    read_v[u] = (4 * h + (i16 >> 2)) * 256 +
+                16 * ((4 * u + 2 * ((lane >> 4) & 1u) + ((i16 >> 1) & 1u)) ^ (i16 & 12u)) +
+                8 * (i16 & 1u);
+  const uint32_t my_query = 32 * wave + r;  // within the workgroup's 128
+  const uint64_t q_row = static_cast<uint64_t>(head) * seq + qt * kAttnRows + my_query;
+  const int4v* pq = q + q_row * kAttnRowVecs + h;
+
+  const auto load = [](int4v rsrc, const int4v* lds, uint32_t lane_off, uint32_t shared_off)
+      __attribute__((always_inline)) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+                 :
+                 : "s"(static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsPtr)lds))),
+                   "v"(lane_off), "s"(rsrc), "s"(shared_off)
+                 : "memory", "m0");
+  };
+  // The eight loads of tile `at` into the pair `to`.
+  const auto issue = [&](const int4v (*to)[kAttnTileVecs], uint32_t at)
+      __attribute__((always_inline)) {
+    const uint32_t outside = at < tiles ? 0u : kBufferOutside;
+    const uint32_t tile_off = at * (kAttnKeys * 256);
+#pragma unroll
+    for (int i = 0; i < kAttnLoads; ++i) {
+      load(rk, to[0] + land_at + 16 * kAttnRowVecs * i, load_k | outside, tile_off + 16 * 256 * i);
+      load(rv, to[1] + land_at + 16 * kAttnRowVecs * i, load_v | outside, tile_off + 16 * 256 * i);
+    }
+  };
+  const auto landed = [] {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  };
+
+  bf16x8 qf[8];
+  f32x16 out[4];
+  float m = -__builtin_inff(), l = 0.0f;
+  // One tile: scores, online softmax, output.
+  const auto step = [&](const int4v (*from)[kAttnTileVecs], uint32_t at)
+      __attribute__((always_inline)) {
+    f32x16 s[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) s[t][reg] = 0.0f;
+#pragma unroll
+    for (uint32_t sub = 0; sub < 8; ++sub) {
+      const uint32_t c = (2 * sub + h) ^ read_key;
+#pragma unroll
+      for (uint32_t t = 0; t < 2; ++t) {
+        const bf16x8 kf =
+            __builtin_bit_cast(bf16x8, from[0][read_k + 32 * kAttnRowVecs * t + c]);
+        s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[sub], s[t], 0, 0, 0);
+      }
+    }
+    if (at + 2 >= tiles) {  // a diagonal tile: its keys start at 0 or 64 of the 128
+      const uint32_t key0 = 64 * (at + 2 - tiles) + 4 * h;
+#pragma unroll
+      for (uint32_t t = 0; t < 2; ++t)
+#pragma unroll
+        for (uint32_t reg = 0; reg < 16; ++reg)
+          if (key0 + 32 * t + (reg & 3u) + 8 * (reg >> 2) > my_query)
+            s[t][reg] = -__builtin_inff();
+    }
+    float top = s[0][0];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) top = __builtin_fmaxf(top, s[t][reg]);
+    const f32x2 tops = attn_pair(top);
+    const float m_new = __builtin_fmaxf(m, __builtin_fmaxf(tops[0], tops[1]));
+    const float alpha = __builtin_amdgcn_exp2f((m - m_new) * kAttnScale);
+    m = m_new;
+    bf16x8 p[2][2];  // [t][g]: registers 8 g .. 8 g + 7 of s[t]
+    float sum = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const float e = __builtin_amdgcn_exp2f((s[t][reg] - m) * kAttnScale);
+        sum += e;
+        p[t][reg >> 3][reg & 7] = static_cast<__bf16>(e);
+      }
+    l = l * alpha + sum;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) out[u][reg] *= alpha;
+    const char* tile_v = reinterpret_cast<const char*>(from[1]);
+#pragma unroll
+    for (uint32_t tg = 0; tg < 4; ++tg) {  // keys 16 tg ..: t = tg >> 1, g = tg & 1
+#pragma unroll
+      for (uint32_t u = 0; u < 4; ++u) {
+        short4v half[2];
+#pragma unroll
+        for (uint32_t x = 0; x < 2; ++x)
+          half[x] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (__attribute__((address_space(3))) short4v*)(tile_v + read_v[u] +
+                                                           (16 * tg + 8 * x) * 256));
+        const short8 vf = __builtin_shufflevector(half[0], half[1], 0, 1, 2, 3, 4, 5, 6, 7);
+        out[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf),
+                                                         p[tg >> 1][tg & 1u], out[u], 0, 0, 0);
+      }
+    }
+  };
+
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  const unsigned long long t0 = stamp_start();
+#pragma unroll
+  for (int sub = 0; sub < 8; ++sub) qf[sub] = __builtin_bit_cast(bf16x8, pq[2 * sub]);
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) out[u][reg] = 0.0f;
+  issue(ring[0], 0);
+  landed();
+  // Q is in its registers here, and the compiler knows it: it counts its own
+  // loads only, so a wait for Q that it placed at the first use, inside the
+  // loop, would be a wait for the tile just issued in every step.
+  asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]), "+v"(qf[4]),
+               "+v"(qf[5]), "+v"(qf[6]), "+v"(qf[7]));
+  for (uint32_t i = 0; i < tiles; ++i) {
+    issue(ring[(i + 1) & 1u], i + 1);
+    step(ring[i & 1u], i);
+    landed();
+  }
+  // O[query][32 u + 8 a + 4 h + 0..3] = registers 4 a .. 4 a + 3 of out[u] / l.
+  const f32x2 sums = attn_pair(l);
+  const float scale = 1.0f / (sums[0] + sums[1]);
+  short4v* po = o + ((static_cast<uint64_t>(pass) * heads * seq + q_row) * kAttnDim) / 4 + h;
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      short4v four;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        four[j] = __builtin_bit_cast(short, static_cast<__bf16>(out[u][4 * a + j] * scale));
+      po[8 * u + 2 * a] = four;
+    }
+  clocked_end(rec, clk, c0, t0);
+}
+#pragma clang diagnostic pop
+
+// What the reference kernel adds up through LDS: the block's maximum, the
+// last operand winning when it is not a number so that one is never lost, or
+// its sum. Every thread gets the result.
+template <bool kMax>
+__device__ inline double attn_reduce(double* red, double x) {
+  __syncthreads();  // red is free again
+  red[threadIdx.x] = x;
+  __syncthreads();
+  for (uint32_t width = kBlock / 2; width > 0; width >>= 1) {
+    if (threadIdx.x < width) {
+      const double a = red[threadIdx.x], b = red[threadIdx.x + width];
+      red[threadIdx.x] = kMax ? ((b > a || b != b) ? b : a) : a + b;
+    }
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__device__ inline double bf16_to_double(unsigned short bits) {
+  return static_cast<double>(__uint_as_float(static_cast<uint32_t>(bits) << 16));
+}
+
+// The plain reference: workgroup b recomputes row samples[3 b + 2] of head
+// samples[3 b + 1] of pass samples[3 b] in fp64 and holds the kernel's O
+// against it. Scores of keys 0 .. row (one key per thread at a time, into the
+// workgroup's own seq doubles of `scratch`), their maximum, exp and the sum,
+// then thread d < 128 the weighted sum over V's column d, divided by the sum.
+// worst is the maximum over all workgroups of |O - reference|, kept as the
+// bits of a non-negative double, which order as the doubles do and put a
+// not-a-number above everything. Every index is below its buffer's size:
+// sample < passes x heads x seq by construction of the samples, key <= row <
+// seq.
+__global__ void __launch_bounds__(kBlock)
+tenant_attention_reference_kernel(const unsigned short* __restrict__ q,
+                                  const unsigned short* __restrict__ k,
+                                  const unsigned short* __restrict__ v,
+                                  const unsigned short* __restrict__ o,
+                                  const uint32_t* __restrict__ samples, uint32_t heads,
+                                  uint32_t seq, double* __restrict__ scratch,
+                                  unsigned long long* __restrict__ worst) {
+  __shared__ double red[kBlock];
+  const uint32_t pass = samples[3 * blockIdx.x], head = samples[3 * blockIdx.x + 1];
+  const uint32_t row = samples[3 * blockIdx.x + 2];
+  const uint64_t head_at = static_cast<uint64_t>(head) * seq * kAttnDim;
+  const unsigned short* qr = q + head_at + static_cast<uint64_t>(row) * kAttnDim;
+  double* score = scratch + static_cast<uint64_t>(blockIdx.x) * seq;
+  double top = -__builtin_inf();
+  for (uint32_t key = threadIdx.x; key <= row; key += kBlock) {
+    const unsigned short* kr = k + head_at + static_cast<uint64_t>(key) * kAttnDim;
+    double dot = 0.0;
+    for (int d = 0; d < kAttnDim; ++d) dot += bf16_to_double(qr[d]) * bf16_to_double(kr[d]);
+    score[key] = dot / sqrt(static_cast<double>(kAttnDim));
+    top = fmax(top, score[key]);
+  }
+  top = attn_reduce<true>(red, top);
+  double sum = 0.0;
+  for (uint32_t key = threadIdx.x; key <= row; key += kBlock) {
+    score[key] = exp(score[key] - top);
+    sum += score[key];
+  }
+  sum = attn_reduce<false>(red, sum);  // its barriers publish score[] to the workgroup
+  double error = 0.0;
+  if (threadIdx.x < kAttnDim) {
+    double acc = 0.0;
+    for (uint32_t key = 0; key <= row; ++key)
+      acc += score[key] * bf16_to_double(v[head_at + static_cast<uint64_t>(key) * kAttnDim +
+                                           threadIdx.x]);
+    const uint64_t at = (static_cast<uint64_t>(pass) * heads * seq * kAttnDim) + head_at +
+                        static_cast<uint64_t>(row) * kAttnDim + threadIdx.x;
+    error = fabs(bf16_to_double(o[at]) - acc / sum);
+  }
+  error = attn_reduce<true>(red, error);
+  if (threadIdx.x == 0)
+    atomicMax(worst, static_cast<unsigned long long>(__double_as_longlong(error)));
+}
+
 // ---- host ------------------------------------------------------------------
 
 enum class Kind : int {
   kFma, kStream, kCache, kChase, kMfma, kGemm, kGemmMxfp8, kGemmMxfp4, kDecodeMxfp8,
-  kDecodeMxfp4
+  kDecodeMxfp4, kAttention
 };
-constexpr int kKinds = 10;
+constexpr int kKinds = 11;
 // What a kind shares with others: nothing (plain), form and operands (mfma),
-// the bf16 GEMM, a block-scaled GEMM, or the decode shape of one.
-enum class Family : int { kPlain, kMfma, kGemm, kMxGemm, kDecode };
+// the bf16 GEMM, a block-scaled GEMM, the decode shape of one, or attention.
+enum class Family : int { kPlain, kMfma, kGemm, kMxGemm, kDecode, kAttention };
 // Per kind: the kind itself (the table is indexed by it), name, family, the
 // form a block-scaled kind implies (kBf16 otherwise), workgroups per CU
-// (chase: one, that is one wave per SIMD; the gemms: none, their grid is the
-// problem's), whether it reads a buffer filled beforehand, whether its
+// (chase: one, that is one wave per SIMD; the gemms and attention: none, their
+// grid is the problem's), whether it reads a buffer filled beforehand, whether its
 // launches carry clocks.
 struct KindInfo {
   Kind kind;
@@ -2057,7 +2493,8 @@ constexpr KindInfo kKindTable[kKinds] = {
     {Kind::kGemmMxfp8, "gemm-mxfp8", Family::kMxGemm, kMxfp8, 0, true, true},
     {Kind::kGemmMxfp4, "gemm-mxfp4", Family::kMxGemm, kMxfp4, 0, true, true},
     {Kind::kDecodeMxfp8, "decode-mxfp8", Family::kDecode, kMxfp8, 0, true, true},
-    {Kind::kDecodeMxfp4, "decode-mxfp4", Family::kDecode, kMxfp4, 0, true, true}};
+    {Kind::kDecodeMxfp4, "decode-mxfp4", Family::kDecode, kMxfp4, 0, true, true},
+    {Kind::kAttention, "attention", Family::kAttention, kBf16, 0, true, true}};
 constexpr bool kind_table_in_order() {
   for (int i = 0; i < kKinds; ++i)
     if (static_cast<int>(kKindTable[i].kind) != i) return false;
@@ -2145,8 +2582,13 @@ struct TenantResult {
   uint64_t m = 0, n = 0, k = 0;    // gemm only
   uint64_t scale_bytes = 0;        // block-scaled gemm only: A's and B's scale words
   uint64_t lead_bytes = 0;         // decode only: A's elements, in the buffer before W's
-  uint64_t load_bytes_per_launch = 0;  // gemm only
-  // flops (fma, mfma, gemm), bytes (stream, cache) or hops (chase)
+  uint64_t load_bytes_per_launch = 0;  // gemm and attention only
+  // attention only: rows and heads, every pass's O, the reference kernel's
+  // scores, the rows it recomputed and the largest |O - reference| it found
+  uint64_t seq = 0, heads = 0, out_bytes = 0, scratch_bytes = 0;
+  int checked_rows = 0;
+  double max_error = 0.0;
+  // flops (fma, mfma, gemm, attention), bytes (stream, cache) or hops (chase)
   double work_per_launch = 0.0;
   double bytes_per_cu = 0.0;     // cache only
   std::vector<Launch> launches;
@@ -2285,8 +2727,78 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
           (kGemmTile * 128 + kDecodeRows * 128 + 2 * kWavesPerGroup * kDecodeRows * mx.word_bytes);
       break;
     }
+    case Kind::kAttention: {
+      // agent/cotenancy.py states the same rule on its own (attention_shape).
+      // A row of Q plus one of K plus one of V is 768 bytes.
+      if (iters <= 0) iters = kAttnDefaultIters;
+      r.iters = std::min(iters, kAttnMaxIters);  // query tiles of 128 rows
+      r.seq = static_cast<uint64_t>(kAttnRows) * r.iters;
+      const uint64_t heads = bytes == 0 ? kAttnDefaultHeads : bytes / (768 * r.seq);
+      r.heads = std::min<uint64_t>(std::max<uint64_t>(heads, 1), kAttnMaxHeads);
+      r.bytes = 768 * r.seq * r.heads;
+      // The GEMMs' clamp of passes and their grid, with heads x query tiles as
+      // the "tiles" of a pass (nothing divides by r.tiles here: r.out stays
+      // empty); the flops it leaves are for m = n = k = 0 and are set below.
+      plan_gemm_grid(r, static_cast<int>(r.heads) * r.iters, passes, kAttnDefaultPasses);
+      r.out_bytes = 256 * r.seq * r.heads * r.passes;
+      const uint64_t rows = r.seq * r.heads * r.passes;
+      r.checked_rows = static_cast<int>(std::min<uint64_t>(rows, kAttnSamples));
+      r.scratch_bytes = r.checked_rows * r.seq * sizeof(double);
+      // Two flops for Q K^T and two for P V per pair (row, key <= row); the
+      // masked half of a diagonal tile is issued but not counted.
+      r.work_per_launch = 4.0 * kAttnDim * (0.5 * r.seq * (r.seq + 1)) * r.heads * r.passes;
+      // Per workgroup on query tile qt its 128 rows of Q and 2 (qt + 1) tiles of
+      // K and of V, 32 KiB each: over qt < T, T + T (T + 1) of them.
+      r.load_bytes_per_launch = static_cast<uint64_t>(r.passes) * r.heads * 32768 *
+                                r.iters * (r.iters + 2);
+      break;
+    }
   }
   return r;
+}
+
+// The rows the reference kernel recomputes, as (pass, head, row) triples: all
+// of them when there are no more than kAttnSamples; otherwise rows 0 and seq -
+// 1 of head 0 in the first and in the last pass, and the rest hashed from
+// the seed and the sample's index.
+std::vector<uint32_t> attention_samples(const TenantResult& r, uint64_t seed) {
+  const uint32_t seq = static_cast<uint32_t>(r.seq), heads = static_cast<uint32_t>(r.heads);
+  const uint32_t passes = static_cast<uint32_t>(r.passes);
+  const bool all = r.seq * r.heads * r.passes <= kAttnSamples;
+  const uint32_t key = mix32(static_cast<uint32_t>(seed) ^ kAttnKeySalt);
+  std::vector<uint32_t> out;
+  for (uint32_t i = 0; i < static_cast<uint32_t>(r.checked_rows); ++i) {
+    if (all) {
+      out.insert(out.end(), {i / (heads * seq), i / seq % heads, i % seq});
+    } else if (i < 4) {
+      out.insert(out.end(), {i & 2u ? passes - 1 : 0u, 0u, i & 1u ? seq - 1 : 0u});
+    } else {
+      const uint32_t hash = mix32(key ^ i);
+      out.insert(out.end(), {hash % passes, mix32(hash ^ 1u) % heads, mix32(hash ^ 2u) % seq});
+    }
+  }
+  return out;
+}
+
+// The fill and one launch of an attention tenant on `stream`: Q, K and V lie
+// in `buf` one behind the other, `o` takes every pass's O.
+void attention_fill(hipStream_t stream, const TenantResult& r, int cus, void* buf,
+                    uint64_t seed) {
+  hipLaunchKernelGGL(tenant_attention_fill_kernel, dim3(kGroupsPerCu * cus), dim3(kBlock), 0,
+                     stream, static_cast<int4v*>(buf), r.bytes / 16,
+                     static_cast<uint32_t>(r.heads), static_cast<uint32_t>(r.seq),
+                     mix32(static_cast<uint32_t>(seed) ^ kAttnKeySalt));
+  HIP_CHECK(hipGetLastError());
+}
+
+void attention_launch(hipStream_t stream, const TenantResult& r, const void* buf, void* o,
+                      unsigned long long* rec, unsigned long long* clk) {
+  const auto* q = static_cast<const int4v*>(buf);
+  const uint64_t operand = r.bytes / 3 / 16;
+  hipLaunchKernelGGL(tenant_attention_kernel, dim3(r.workgroups), dim3(kBlock), 0, stream, q,
+                     q + operand, q + 2 * operand, static_cast<short4v*>(o),
+                     static_cast<uint32_t>(r.heads), static_cast<uint32_t>(r.iters), rec, clk);
+  HIP_CHECK(hipGetLastError());
 }
 
 // Run: buffers, stream, fill, one untimed launch and `launches` timed ones;
@@ -2307,8 +2819,21 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
   if (is_mxgemm(r.kind)) scales.alloc(r.scale_bytes);
   // {sum of shader cycles, sum of wall ticks} per launch, from zero.
   if (kind_info(r.kind).clocks) clks.h.assign(recs.h.size(), 0ULL);
+  // attention: the rows to recompute, the reference's scores, its one word.
+  DevBuf samples, scratch;
+  std::vector<unsigned long long> worst_word;
+  Mirror worst{worst_word};
   if (r.kind == Kind::kFma) {  // what a lane stores
     out.alloc(lanes * sizeof(float));
+  } else if (r.kind == Kind::kAttention) {  // every pass's O
+    out.alloc(r.out_bytes);
+    const std::vector<uint32_t> rows = attention_samples(r, seed);
+    samples.alloc(rows.size() * sizeof(uint32_t));
+    HIP_CHECK(hipMemcpy(samples.p, rows.data(), rows.size() * sizeof(uint32_t),
+                        hipMemcpyHostToDevice));
+    scratch.alloc(r.scratch_bytes);
+    worst_word.assign(1, 0ULL);
+    worst.copy(true);
   } else {
     r.out.resize(lanes);
     out.alloc(lanes * sizeof(unsigned long long));
@@ -2375,6 +2900,9 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
                   r.tiles, rec, clks.at(2 * slot));
           });
           break;
+        case Kind::kAttention:
+          attention_launch(g.s, r, buf.p, out.p, rec, clks.at(2 * slot));
+          break;
       }
     };
     switch (r.kind) {  // the fill
@@ -2404,6 +2932,9 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
              mix32(static_cast<uint32_t>(seed) ^ kGemmKeySalt));
         });
         break;
+      case Kind::kAttention:
+        attention_fill(g.s, r, cus, buf.p, seed);
+        break;
       case Kind::kFma:
       case Kind::kMfma:
         break;
@@ -2416,9 +2947,19 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
       launch(l);
       HIP_CHECK(hipEventRecord(ev[2 * l + 1].e, g.s));
     }
+    if (r.kind == Kind::kAttention) {  // the last launch's O against fp64, not timed
+      const auto* q = buf.as<const unsigned short>();
+      const uint64_t operand = r.bytes / 3 / 2;
+      go(dim3(r.checked_rows), tenant_attention_reference_kernel, q, q + operand,
+         q + 2 * operand, out.as<const unsigned short>(), samples.as<const uint32_t>(),
+         static_cast<uint32_t>(r.heads), static_cast<uint32_t>(r.seq), scratch.as<double>(),
+         worst.at(0));
+    }
     HIP_CHECK(hipStreamSynchronize(g.s));
     recs.copy(false);
     clks.copy(false);
+    worst.copy(false);
+    if (!worst_word.empty()) std::memcpy(&r.max_error, &worst_word[0], sizeof(double));
     if (!r.out.empty())
       HIP_CHECK(hipMemcpy(r.out.data(), out.p, lanes * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost));
@@ -2487,7 +3028,7 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     r.free_bytes = free_b;
-    if (free_b < r.lead_bytes + r.bytes + r.scale_bytes + kGiB) {
+    if (free_b < r.lead_bytes + r.bytes + r.scale_bytes + r.out_bytes + r.scratch_bytes + kGiB) {
       r.skipped = true;
       return r;
     }
@@ -2621,6 +3162,17 @@ void register_cotenant(py::module_& m) {
             }
             if (r.tiled) d["weights"] = weights;
             break;
+          case Family::kAttention:
+            d["seq"] = r.seq;
+            d["heads"] = r.heads;
+            d["head_dim"] = kAttnDim;
+            d["bytes"] = r.bytes;
+            d["out_bytes"] = r.out_bytes;
+            d["passes"] = r.passes;
+            d["max_error"] = r.max_error;
+            d["checked_rows"] = r.checked_rows;
+            d["load_bytes_per_launch"] = r.load_bytes_per_launch;
+            break;
         }
         if (clocks) last["clock_ghz"] = r.clock_ghz;
         d["work_per_launch"] = r.work_per_launch;
@@ -2653,8 +3205,8 @@ void register_cotenant(py::module_& m) {
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
       "\"cache\", \"chase\", \"mfma\", \"gemm\", \"gemm-mxfp8\", \"gemm-mxfp4\", "
-      "\"decode-mxfp8\" or \"decode-mxfp4\", anything else raises ValueError "
-      "before the device is touched. After one untimed "
+      "\"decode-mxfp8\", \"decode-mxfp4\" or \"attention\", anything else raises "
+      "ValueError before the device is touched. After one untimed "
       "launch, `launches` (1..64) launches of the same work run back to back "
       "on one stream, each between its own pair of events; the grid is 32 x "
       "CUs workgroups of 256 lanes (cache: 8 x CUs, all resident at once; "
@@ -2939,11 +3491,67 @@ void register_cotenant(py::module_& m) {
       "stay as they are, the product and so the checksum are the same, and "
       "so is every shape and byte key; the result adds weights = \"tiled\" "
       "after load_bytes_per_launch.\n\n"
+      "attention: a causal flash-attention forward pass in bf16, per head O = "
+      "softmax(Q K^T / sqrt(128), causal) V with row i attending to keys 0 .. i, "
+      "head dimension 128, Q, K, V and O row-major [head][row][128]: the matrix "
+      "pipe and the transcendental unit busy in one wave, and K and V re-read "
+      "out of the caches by every query tile of their head. `iters` is the "
+      "sequence length in units of 128 rows (default 64: seq = 8192; clamped to "
+      "1 .. 256); `bytes` is Q plus K plus V, heads = bytes // (768 seq) clamped "
+      "to 1 .. 1024 (0: 64 heads), and the result reports the bytes really "
+      "used, 768 seq heads; `passes` is the whole forward passes of one launch, "
+      "each into its own O (default 8, a default launch lasting about as long "
+      "as gemm's; clamped to 1 .. 2^22 // (heads iters)). "
+      "O, 256 seq heads passes bytes, is reported as out_bytes and is no part "
+      "of bytes; the free-memory refusal counts bytes, out_bytes and the "
+      "reference's 8 seq checked_rows. The grid is passes x heads x iters "
+      "workgroups; workgroup g of a pass owns the 128 query rows of tile iters "
+      "- 1 - g // heads of head g % heads, the longest first, each of its four "
+      "waves 32 rows. K and V come in tiles of 64 keys, 16 KiB each, from memory "
+      "straight to a ring of two {K, V} pairs in LDS (the 16-byte LDS-DMA load "
+      "of gemm's `loads` \"direct\", its wait and its one barrier per tile; 64 "
+      "KiB, two workgroups per CU); tiles above the diagonal are never loaded, "
+      "so a workgroup runs 2 (tile + 1) of them and a launch has a tail. Per "
+      "tile a wave computes S^T = K Q^T, 64 keys x 32 queries, in 16 "
+      "v_mfma_f32_32x32x16_bf16 with Q held in registers; a lane then holds 32 "
+      "keys of one query column, so the row maximum is an in-lane one and one "
+      "v_permlane32_swap. The softmax is online and in base 2, p = exp2((s - m) "
+      "c) with c = log2(e) / sqrt(128) through v_exp_f32, running maximum and "
+      "sum in f32; the last two tiles of a workgroup set the scores beyond the "
+      "diagonal to -inf first. P is rounded to bf16 in registers and is as it "
+      "stands the B operand of O^T = V^T P^T, 16 more MFMAs into a 128 x 32 "
+      "accumulator; V^T comes from the row-major V tile with the transposing "
+      "LDS read ds_read_b64_tr_b16, in the key order P's registers have. O is "
+      "divided by the sum once and stored as bf16. Q, K and V are written once "
+      "on the same stream before anything is timed: key = mix32(mix32(seed32 ^ "
+      "0x4154544E) ^ which * 0x9E3779B1 ^ head), which = 0, 1, 2, and the "
+      "element at [row][d] is (mix32(key ^ (row << 7 | d)) % 31 - 15) / 8, / 4 "
+      "or / 16, exact in bf16, every score exact in f32, and a row's softmax "
+      "weighing a few keys so that a dropped tile or a mask off by one moves "
+      "the output far. The output is no integer and there is no checksum: "
+      "after the timed launches a plain fp64 kernel (one workgroup a row: the "
+      "scores, their maximum, exp, the sum, the weighted sum; no MFMA, no LDS "
+      "tiling, no online softmax) recomputes checked_rows = min(256, passes "
+      "heads seq) rows of the last launch's O, (pass, head, row) hashed from "
+      "`seed` and the sample's index with rows 0 and seq - 1 of head 0 of the "
+      "first and the last pass always among them, and max_error is the "
+      "largest |O - reference| over their elements (agent/cotenancy.py, "
+      "ATTENTION_TOLERANCE, is what it may be). Clocks as for mfma. The result "
+      "has seq, heads, head_dim, bytes, out_bytes, passes, max_error, "
+      "checked_rows, load_bytes_per_launch = passes heads 32768 iters (iters + "
+      "2), Q once and the K and V tiles of every workgroup, work_per_launch = "
+      "passes heads 4 x 128 seq (seq + 1) / 2 flops, two for Q K^T and two for P "
+      "V per pair of a row and a key it sees (the masked half of a diagonal "
+      "tile is issued but not counted), rates in GFLOP/s and the clocks. It "
+      "takes no form, operands, loads or weights. attention_output returns "
+      "every element of one pass's O.\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
       "{kind, [form,] applied_mask, tick_hz, workgroups, iters | [m, n, k,] bytes, "
-      "[scale_bytes,] passes, "
+      "[scale_bytes,] passes, (attention: seq, heads, head_dim, bytes, out_bytes, "
+      "passes, max_error, checked_rows, load_bytes_per_launch in place of these "
+      "and of what follows up to work_per_launch) "
       "checksum, [load_bytes_per_launch, [loads, stages, lds_bytes,] [weights,]] "
       "[operands, lds_bytes, lds_bytes_per_launch,] "
       "[bytes_per_cu,] work_per_launch: flops, bytes or hops, launches: [{t0, t1, "
@@ -2955,4 +3563,49 @@ void register_cotenant(py::module_& m) {
       "and cache) is the XOR of the words the last launch's lanes stored and "
       "equals "
       "pattern_xor(seed, 0, bytes // 8) when every byte was read.");
+
+  m.def(
+      "attention_output",
+      [](int device, py::object mask, int iters, uint64_t bytes, uint64_t seed) {
+        const MaskWords raw = gpuprobe::mask_from_python(mask);
+        // The plan depends on no device; the fill's grid alone takes its CUs.
+        TenantResult r = plan_tenant(Kind::kAttention, 0, iters, bytes, 1, kBf16, false, false,
+                                     false);
+        if (r.out_bytes > kAttnMaxOutput)
+          throw py::value_error("attention_output: the output of " + std::to_string(r.heads) +
+                                " heads of " + std::to_string(r.seq) + " rows is " +
+                                std::to_string(r.out_bytes) + " bytes, more than 64 MiB");
+        std::string o(r.out_bytes, '\0');
+        {
+          py::gil_scoped_release release;
+          require_device(device);
+          const int cus = gpuprobe::device_cus(device);
+          const MaskWords words = raw.empty() ? MaskWords{} : gpuprobe::fit_mask(raw, cus);
+          DevBuf buf, out;
+          std::vector<unsigned long long> stamps{~0ULL, 0ULL, 0ULL, 0ULL};  // rec, clk
+          Mirror marks{stamps};
+          buf.alloc(r.bytes);
+          out.alloc(r.out_bytes);
+          marks.copy(true);
+          HIP_CHECK(hipDeviceSynchronize());
+          StreamGuard g;
+          gpuprobe::open_stream(g, words, r.applied);
+          attention_fill(g.s, r, cus, buf.p, seed);
+          attention_launch(g.s, r, buf.p, out.p, marks.at(0), marks.at(2));
+          HIP_CHECK(hipStreamSynchronize(g.s));
+          HIP_CHECK(hipMemcpy(o.data(), out.p, r.out_bytes, hipMemcpyDeviceToHost));
+        }
+        py::dict d;
+        d["seq"] = r.seq;
+        d["heads"] = r.heads;
+        d["output"] = py::bytes(o);
+        return d;
+      },
+      py::arg("device") = 0, py::arg("mask") = py::none(), py::arg("iters") = 0,
+      py::arg("bytes") = 0, py::arg("seed") = 1,
+      "What one pass of an attention tenant computes: the fill and one launch of "
+      "cu_tenant_run(kind=\"attention\")'s kernel for the same `iters`, `bytes` "
+      "and `seed`, one pass. Returns {seq, heads, output}, output being O as "
+      "little-endian bf16, [head][row][128], 256 * seq * heads bytes; raises "
+      "ValueError before the device is touched when that is more than 64 MiB.");
 }
