@@ -497,6 +497,12 @@ class NodeAgent:
         fp64 reference, and an error above cotenancy.ATTENTION_TOLERANCE makes
         the report not ok ("bad-output"). Its entries carry the clock and its
         split, and it takes none of form, operands, loads and weights.
+        pairs=cotenancy.attention_decode_pairs() brings in the decode half of
+        attention, 16 query rows against a head's K and V streamed from
+        memory once and split along the keys (window: iters = capacity / 128,
+        bytes of Q + K + V, passes), beside itself, the streamer, the prefill
+        attention and decode-mxfp4, both ways round; verified, split and
+        refused the options as the attention kind is.
 
         The masks come from a scratch plan over the measured layout; the
         live plan is not touched. As in verify_masks, nothing is launched

@@ -100,7 +100,19 @@ checksum: the probe recomputes 256 sampled rows in fp64 after the timed
 launches and reports max_error, which a report holds against
 ATTENTION_TOLERANCE. It reports the clock it saw and a pair splits its ratio
 as for the GEMM kinds; it takes neither form nor operands nor loads nor
-weights. WORKLOAD_KINDS is every kind a child can be started as.
+weights. WORKLOAD_KINDS is the kinds up to here.
+
+"attention-decode" (ATTENTION_DECODE_KINDS, SERVING_KINDS,
+attention_decode_pairs()) is the other half of attention, a decode step's: the
+16 query rows of one step (a grouped-query group of 16) attend to a head's K
+and V, which are read from HBM exactly once per pass, the work split along the
+keys, MFMA, v_exp_f32 and LDS at memory speed. Head h is live for
+attention_decode_length(h, seq) keys, so the lengths are ragged. Its window is
+`iters` (the capacity in units of 128 keys, 0: 8192), `bytes` (Q plus K plus
+V, 0: 256 heads, 1 GiB of K and V) and `passes`; attention_decode_shape()
+states the shape and the splits, attention_operands() the data (Q is its rows
+0..15). It is verified, reports its clock and refuses the four options as the
+attention kind does. SERVING_KINDS is every kind a child can be started as.
 
 Concurrency comes from processes only: each child has one stream, and no
 child is ever started after one has failed.
@@ -192,8 +204,49 @@ ATTENTION_HEAD_DIM = 128
 # bf16 store) at seq 128, 384 and 1024 stays within 0.0031 with truncation and
 # 0.0024 with round-to-nearest, while dropping one K/V tile moves 99-100 % of
 # the rows behind it beyond 2^-7 and a mask one key too wide 10-41 % of all
-# rows.
+# rows. The decode shape keeps the derivation: its weights are normalised, |v|
+# <= 15/16 holds, and the f32 merges of the waves and of the splits under their
+# common maximum add nothing of size. The emulation was not re-run with the
+# split merge; on the card the kernel's every-element tests at seq 128 .. 2176
+# stayed within 0.0023.
 ATTENTION_TOLERANCE = 2 ** -7
+
+
+# The kind that is a decode step's attention (split-KV, K and V streamed once),
+# and every kind a child can be started as.
+ATTENTION_DECODE_KINDS = ("attention-decode",)
+SERVING_KINDS = WORKLOAD_KINDS + ATTENTION_DECODE_KINDS
+ATTENTION_DECODE_QUERIES = 16
+
+
+def attention_decode_pairs() -> Tuple[Tuple[str, str], ...]:
+    """The pairs that say what a neighbour does to an attention-decode tenant
+    and what it does to them: another such tenant, the streamer, the prefill
+    attention and the decode-mxfp4 GEMM, both ways round each."""
+    kind, others = ATTENTION_DECODE_KINDS[0], ("stream", "attention", "decode-mxfp4")
+    return ((kind, kind),) + tuple(
+        pair for other in others for pair in ((kind, other), (other, kind)))
+
+
+def attention_decode_shape(bytes: int = 0, iters: int = 0) -> Tuple[int, int, int, int]:
+    """(heads, seq, 128, splits) of the step an attention-decode tenant runs
+    for the window keys `bytes` and `iters`, the probe's rule stated on its
+    own: seq = 128 * iters (0: 64; clamped to 1 .. 256), heads = bytes // (512 *
+    seq + 4096), a key's row of K and of V being 512 bytes and a head's 16 rows
+    of Q 4096 (0: 256 heads), clamped to 1 .. 1024, and splits = 2048 // heads
+    clamped to 1 .. ceil(iters / 8); a split is ceil(iters / splits) units of
+    128 keys."""
+    units = min(int(iters), 256) if int(iters) > 0 else 64
+    seq = 128 * units
+    heads = int(bytes) // (512 * seq + 4096) if int(bytes) else 256
+    heads = min(max(heads, 1), 1024)
+    return heads, seq, ATTENTION_HEAD_DIM, min(max(2048 // heads, 1), -(-units // 8))
+
+
+def attention_decode_length(head: int, seq: int) -> int:
+    """The live keys of `head` of an attention-decode tenant: keys 0 .. this -
+    1 count, the rest of the `seq` are in memory and must not."""
+    return int(seq) - (37 * int(head)) % 128
 
 
 def attention_pairs() -> Tuple[Tuple[str, str], ...]:
@@ -620,7 +673,7 @@ def _child_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="cotenancy", description=__doc__)
     p.add_argument("--child", action="store_true", required=True)
     p.add_argument("--device", type=int, default=0)
-    p.add_argument("--kind", choices=WORKLOAD_KINDS, default="fma")
+    p.add_argument("--kind", choices=SERVING_KINDS, default="fma")
     p.add_argument("--launches", type=int, default=8)
     p.add_argument("--iters", type=int, default=0)
     p.add_argument("--bytes", type=int, default=0)
@@ -759,7 +812,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     """Run up to two tenants at once on `card`, each a fresh child process
     under ROC_GLOBAL_CU_MASK = its mask. A tenant is {"mask": int, "kind":
     "fma" | "stream" | "cache" | "chase" | "mfma" | "gemm" | "gemm-mxfp8" |
-    "gemm-mxfp4" | "decode-mxfp8" | "decode-mxfp4" | "attention"} and may
+    "gemm-mxfp4" | "decode-mxfp8" | "decode-mxfp4" | "attention" |
+    "attention-decode"} and may
     carry its own "launches", "iters",
     "bytes" and "passes" in place of the call-wide ones; `kinds`, when given,
     names the kinds instead. Every child warms up and says READY; only then
@@ -795,8 +849,8 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     "weights" on a tenant of any other kind raises ValueError before
     anything is started, the call-wide value leaves the other kinds as they
     are, and a child is given --weights, after --loads, only when one was
-    named for it. An attention tenant takes none of the four: its child is
-    started with its window alone.
+    named for it. An attention or attention-decode tenant takes none of the
+    four: its child is started with its window alone.
 
     Each child has `timeout` seconds from its start. The first child that
     times out, exits non-zero or prints no TENANT line ends the run: the
@@ -822,7 +876,7 @@ def run_pair(card: int, tenants: Sequence[Mapping[str, Any]],
     try:
         for i, tenant in enumerate(tenants):
             kind = kinds[i] if kinds is not None else tenant["kind"]
-            if kind not in WORKLOAD_KINDS:
+            if kind not in SERVING_KINDS:
                 raise ValueError(f"unknown tenant kind {kind!r}")
             env = dict(os.environ)
             env[ENV_CU_MASK] = mask_hex(int(tenant["mask"]))
@@ -895,7 +949,7 @@ def _balanced(launches: int, seconds: Sequence[float]) -> List[int]:
 # solo entry adds; a kind that adds clock_ghz gets the clock split in a pair.
 _SOLO_KEYS = {"chase": ("ns_per_hop",), "mfma": ("clock_ghz",), "gemm": ("clock_ghz",),
               **{kind: ("clock_ghz",) for kind in MXGEMM_KINDS + DECODE_KINDS},
-              "attention": ("clock_ghz",)}
+              "attention": ("clock_ghz",), "attention-decode": ("clock_ghz",)}
 
 
 def _expected(result: Mapping[str, Any], seed: int, pattern, form=None,
@@ -1009,6 +1063,14 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     its split as a gemm tenant's do. It takes none of `form`, `operands`,
     `loads` and `weights`.
 
+    An attention-decode tenant (pairs=attention_decode_pairs()) is a decode
+    step's attention, 16 query rows against K and V streamed once per pass:
+    `iters` is the capacity in units of 128 keys, `bytes` Q plus K plus V,
+    `passes` whole steps per launch, see attention_decode_shape(). Its rates
+    are GFLOP/s, 4 x 128 x 16 flop per live key, that is 16 flop per byte of K
+    and V, so rate / 16 is the GB/s it streams. Verified, split into clock and
+    cycles and refused the four options as an attention tenant is.
+
     `form` (one of MFMA_FORMS, anything else raises ValueError) is the
     instruction the mfma tenants issue, alone and in every pair; a tenant
     ({"mask": int, "form": str}) may name its own instead, for a bf16 tenant
@@ -1057,11 +1119,11 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
     if len(tenants) != 2:
         raise ValueError("isolation_report takes two tenants")
     for pair in pairs:
-        if len(pair) != 2 or any(k not in WORKLOAD_KINDS for k in pair):
+        if len(pair) != 2 or any(k not in SERVING_KINDS for k in pair):
             raise ValueError(f"not a pair of tenant kinds: {pair!r}")
     windows = {kind: dict(w) for kind, w in (windows or {}).items()}
     for kind, w in windows.items():
-        if kind not in WORKLOAD_KINDS or any(k not in WINDOW_KEYS for k in w):
+        if kind not in SERVING_KINDS or any(k not in WINDOW_KEYS for k in w):
             raise ValueError(f"not a window of a tenant kind: {kind!r}: {w!r}")
     # Per option and tenant, what the tenant is started with as a tenant of
     # the option's kind.
@@ -1098,13 +1160,13 @@ def isolation_report(card: int, tenants: Sequence[Mapping[str, Any]], *,
             return "bad-checksum"
         # An attention tenant has no checksum: the probe's own fp64 reference
         # says how far its output is off (a not-a-number is not within).
-        if result["kind"] in ATTENTION_KINDS and not (
+        if result["kind"] in ATTENTION_KINDS + ATTENTION_DECODE_KINDS and not (
                 result["max_error"] <= ATTENTION_TOLERANCE):
             return "bad-output"
         return None
 
     for i, tenant in enumerate(tenants):
-        for kind in WORKLOAD_KINDS:
+        for kind in SERVING_KINDS:
             if not any(pair[i] == kind for pair in pairs):
                 continue
             run = run_pair(card, [{"mask": tenant["mask"], "kind": kind,

@@ -37,6 +37,9 @@ memory, beside itself, the streamer and the prefill GEMM;
 order its waves consume them, as production decode GEMMs keep theirs.
 --co-tenancy-attention runs a causal flash-attention forward pass, the other
 prefill kernel, beside itself, the streamer, the GEMM and the decode tenant.
+--co-tenancy-attention-decode runs a decode step's attention, 16 query rows
+against K and V streamed once, beside itself, the streamer, the prefill
+attention and the decode tenant.
 """
 from __future__ import annotations
 
@@ -245,6 +248,19 @@ def build_parser() -> argparse.ArgumentParser:
                         "--co-tenancy-cache, --co-tenancy-chase, "
                         "--co-tenancy-mfma, --co-tenancy-gemm or "
                         "--co-tenancy-decode")
+    p.add_argument("--co-tenancy-attention-decode", action="store_true",
+                   help="with --co-tenancy: instead of the FMA and stream "
+                        "pairs, run a tenant that computes a decode step's "
+                        "attention in bf16 (256 heads of up to 8192 keys, 16 "
+                        "query rows each, head dimension 128: K and V read "
+                        "from memory once, split along the keys, MFMAs, exp2 "
+                        "and LDS at memory speed) next to another such "
+                        "tenant, next to the 1 GiB streamer, next to the "
+                        "prefill attention and next to the decode-mxfp4 "
+                        "tenant (both ways round each), and print one report "
+                        "per card, each ratio split into clock_ratio and "
+                        "cycle_ratio; not together with any other "
+                        "--co-tenancy-* kind flag")
     p.add_argument("--source", default="auto",
                    choices=("auto", "gpuprobe", "amdsmi", "amd-smi",
                             "rocm-smi", "torch"))
@@ -291,7 +307,10 @@ def main(argv=None) -> int:
             ("--co-tenancy-decode-weights", "--co-tenancy-decode", ()),
             ("--co-tenancy-attention", "--co-tenancy",
              ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma",
-              "--co-tenancy-gemm", "--co-tenancy-decode"))):
+              "--co-tenancy-gemm", "--co-tenancy-decode")),
+            ("--co-tenancy-attention-decode", "--co-tenancy",
+             ("--co-tenancy-cache", "--co-tenancy-chase", "--co-tenancy-mfma",
+              "--co-tenancy-gemm", "--co-tenancy-decode", "--co-tenancy-attention"))):
         if not given(flag):
             continue
         if not given(needs):
@@ -304,13 +323,15 @@ def main(argv=None) -> int:
 
     if args.co_tenancy is not None:
         from elastic_gpu_scheduler_amd.agent.cotenancy import (
-            CACHE_PAIRS, CHASE_PAIRS, GEMM_PAIRS, MFMA_PAIRS, attention_pairs, cache_passes,
-            decode_pairs, mxgemm_pairs)
+            CACHE_PAIRS, CHASE_PAIRS, GEMM_PAIRS, MFMA_PAIRS, attention_decode_pairs,
+            attention_pairs, cache_passes, decode_pairs, mxgemm_pairs)
 
         # What every report of the run is asked for and, where a flag names
         # several forms or sizes, what each of them adds, by its label.
         common, each = {}, None
-        if args.co_tenancy_attention:
+        if args.co_tenancy_attention_decode:
+            common = {"pairs": attention_decode_pairs()}
+        elif args.co_tenancy_attention:
             common = {"pairs": attention_pairs()}
         elif args.co_tenancy_decode is not None:
             each = {form: {"pairs": decode_pairs("decode-" + form)}

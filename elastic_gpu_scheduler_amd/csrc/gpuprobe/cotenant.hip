@@ -2054,24 +2054,26 @@ __device__ inline short exact_bf16_bits(float v) {
   return static_cast<short>(__float_as_uint(v) >> 16);
 }
 
-// The operands of an attention tenant: `buf` is Q, then K, then V, each
-// [head][row][128] bf16. key = mix32(seed_key ^ which * 0x9E3779B1 ^ head) with
+// The operands of an attention tenant: `buf` is Q, [head][q_rows][128] bf16,
+// then K, then V, each [head][seq][128] (the prefill kind: q_rows = seq; the
+// decode kind: 16). key = mix32(seed_key ^ which * 0x9E3779B1 ^ head) with
 // which = 0, 1, 2 and seed_key = mix32(seed32 ^ 0x4154544E); the element at
 // [row][d] is (mix32(key ^ (row << 7 | d)) % 31 - 15) / 8, / 4 or / 16: at most
 // four significant bits under a power of two, exact in bf16. One 16-byte store
-// of eight elements per step, grid-stride; n16 = 3 * heads * seq * 16 counts
-// the stores. All indices are 64-bit and below n16; row < 2^15, so row << 7 | d
-// is below 2^22.
+// of eight elements per step, grid-stride; n16 = heads * (q_rows + 2 seq) * 16
+// counts the stores. All indices are 64-bit and below n16; row < 2^15, so row
+// << 7 | d is below 2^22.
 __global__ void __launch_bounds__(kBlock)
 tenant_attention_fill_kernel(int4v* __restrict__ buf, uint64_t n16, uint32_t heads,
-                             uint32_t seq, uint32_t seed_key) {
+                             uint32_t q_rows, uint32_t seq, uint32_t seed_key) {
   uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-  const uint64_t per_head = static_cast<uint64_t>(seq) * kAttnRowVecs;
-  const uint64_t per_operand = per_head * heads;
+  const uint64_t q_vecs = static_cast<uint64_t>(q_rows) * kAttnRowVecs * heads;
+  const uint64_t per_operand = static_cast<uint64_t>(seq) * kAttnRowVecs * heads;
   for (; i < n16; i += stride) {
-    const uint32_t which = static_cast<uint32_t>(i / per_operand);
-    const uint64_t at = i % per_operand;
+    const uint32_t which = i < q_vecs ? 0u : 1u + static_cast<uint32_t>((i - q_vecs) / per_operand);
+    const uint64_t at = i < q_vecs ? i : (i - q_vecs) % per_operand;
+    const uint64_t per_head = static_cast<uint64_t>(which == 0 ? q_rows : seq) * kAttnRowVecs;
     const uint32_t head = static_cast<uint32_t>(at / per_head);
     const uint32_t row = static_cast<uint32_t>(at % per_head / kAttnRowVecs);
     const uint32_t d0 = static_cast<uint32_t>(at % kAttnRowVecs) * 8;
@@ -2385,6 +2387,398 @@ tenant_attention_kernel(const int4v* __restrict__ q, const int4v* __restrict__ k
 }
 #pragma clang diagnostic pop
 
+// ---- attention, the decode shape ---------------------------------------------
+
+// Ring depth per wave, in stages of kAdKeys keys: 2 as built (one workgroup
+// per CU, 128 KiB of LDS), 1 with GPUPROBE_ATTN_DECODE_DEPTH=1 (64 KiB, two
+// workgroups per CU, a wave's loads overlapped by the other seven waves only).
+#ifndef GPUPROBE_ATTN_DECODE_DEPTH
+#define GPUPROBE_ATTN_DECODE_DEPTH 2
+#endif
+constexpr int kAdDepth = GPUPROBE_ATTN_DECODE_DEPTH;
+constexpr int kAdKeys = 32;  // keys per stage: the k of one output MFMA
+static_assert(kAdDepth == 1 || kAdDepth == 2, "160 KiB of LDS hold 4 waves x 2 stages at most");
+static_assert(kAdKeys == 32, "a stage is the 32 keys of one v_mfma_f32_16x16x32_bf16");
+constexpr int kAdQueries = 16;                          // query rows per head
+constexpr int kAdTileVecs = kAdKeys * kAttnRowVecs;     // a stage of K or of V: 8 KiB
+constexpr int kAdLoads = kAdTileVecs / 64;              // loads per lane, operand and stage: 8
+constexpr int kAdSplitFloats = kAdQueries * kAttnDim;   // a split's O, f32
+constexpr uint64_t kAdDefaultHeads = 256;
+constexpr int kAdTargetGroups = 2048;  // splits = this / heads, at least 1024 keys each
+// A default launch on a whole card lasts 6.2 ms beside 8.4-9.2 ms of gemm's in
+// the same run, on half of it 8.2 beside 14.7
+// (profiles/attention_decode_cotenancy_results.md).
+constexpr int kAdDefaultPasses = 32;
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+// The live keys of head `head`: every residue of 128 occurs over 128 heads.
+__host__ __device__ inline uint32_t attn_decode_len(uint32_t head, uint32_t seq) {
+  return seq - (37u * head) % 128u;
+}
+
+// The maximum or the sum of x over the four lanes l, l + 16, l + 32, l + 48,
+// in all four: v_permlane16_swap exchanges the odd rows (of 16 lanes) of its
+// first operand with the even rows of its second, so with both operands x
+// the results are rows {0, 0, 2, 2} and {1, 1, 3, 3} of x; attn_pair does the
+// same for the halves. No LDS round trip, and every lane of the four adds
+// the same numbers in the same order.
+template <bool kMax>
+__device__ inline float attn_quad(float x) {
+  const auto rows = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x),
+                                                     false, false);
+  const float a = __uint_as_float(rows[0]), b = __uint_as_float(rows[1]);
+  const f32x2 halves = attn_pair(kMax ? __builtin_fmaxf(a, b) : a + b);
+  return kMax ? __builtin_fmaxf(halves[0], halves[1]) : halves[0] + halves[1];
+}
+
+// exp2((m - top) c) for a running maximum m that may still be -inf under a
+// maximum `top` that may be -inf too: the difference of two -inf never
+// reaches the exponential, a part without a key weighs 0.
+__device__ inline float attn_weight(float m, float top) {
+  return __builtin_amdgcn_exp2f(m == -__builtin_inff() ? m : (m - top) * kAttnScale);
+}
+
+// The decode step's attention in bf16: 16 query rows (a grouped-query group of
+// 16, or 8 at two speculative positions) of one head attend to the head's live
+// keys, O = softmax(Q K^T / sqrt(128)) V with no mask but the length, head
+// dimension 128, Q [head][16][128], K and V [head][seq][128] row-major. Head h
+// is live for len(h) = seq - 37 h % 128 keys; keys beyond are in memory and
+// must not count. Every byte of K and V is read once per pass and meets the
+// same 16 queries: memory sets the pace, not the matrix pipe.
+//
+// Work split. The grid is passes x heads x splits workgroups, workgroup g on
+// split g % splits of head g / splits % heads; split s owns keys [128 span s,
+// min(128 span (s + 1), len)), `live` of them, possibly none. Nothing is
+// shared between waves, so the split's ceil(live / 32) tiles of 32 keys are
+// dealt round: wave j takes tiles j, j + 4, ..., (tiles - j + 3) / 4 of them or
+// none, into a ring of its own in LDS, with its own running m, l and O^T. No
+// barrier is inside the key loop: a wave waits for its own loads with
+// s_waitcnt vmcnt(n) alone. (That vmcnt's in-order return makes the bytes of
+// an LDS-DMA load visible to a later ds_read of the same wave is read from the
+// ISA description; the every-element test is what confirms it.)
+//
+// Data movement. K and V travel memory -> LDS with tenant_gemm_direct_kernel's
+// 16-byte LDS-DMA load, one wave instruction filling 4 whole rows (8 lines).
+// A stage is 32 keys, 8 KiB of K and 8 KiB of V, 8 + 8 loads per lane, K's
+// first. Step i issues the stage of tile i + kAdDepth - 1 (the prologue those
+// before it), waits until at most 8 + 16 (kAdDepth - 1) loads are outstanding,
+// which is when tile i's K has landed, computes the scores and the softmax,
+// waits for at most 16 (kAdDepth - 1), tile i's V, and adds to the output. The
+// stage a step overwrites was last read one step earlier (depth 1: in this
+// step's predecessor), by this wave alone; an s_waitcnt lgkmcnt(0) in front of
+// the first load of a stage says that those reads have returned. Lane l of
+// instruction n lands on position l & 15 of row R = 4 n + (l >> 4) of the tile
+// and fetches chunk (l & 15) ^ attn_k_key(R); the key depends on n & 3 only, so
+// four lane offsets serve K and V alike. Fragment reads: K as MFMA A operands,
+// ds_read_b128, lane r + 16 g on row 16 t + r at chunk 4 s + g, 16 rows whose
+// keys are all 16 values, or eight rows each of chunk c and c ^ 1, whose keys
+// are the even ones: 16 bank groups either way (attn_k_key's argument). V with
+// ds_read_b64_tr_b16, 32 lanes on 8 consecutive rows (base a multiple of 8) x
+// chunks 2 u and 2 u + 1: the eight keys differ in bits 1..3, so the 16 (row,
+// chunk) pairs take 16 positions and the 32 8-byte reads all 64 banks. So the
+// one key function serves both tiles.
+//
+// Scores. S^T = K Q^T per tile, 32 keys x 16 queries, as two 16 x 16
+// accumulators (keys 16 t ..) over d = 128 in four v_mfma_f32_16x16x32_bf16
+// each: A is K from LDS, B is Q, loaded once (lane r + 16 g: query r, chunk 4 s
+// + g). Lane r + 16 g then holds in register i of accumulator t the score of
+// query r and key 16 t + 4 g + i: a query column's 32 scores sit in four lanes
+// x 8 registers, its maximum is in-lane plus attn_quad.
+//
+// Softmax, online and in base 2 as in the prefill kernel. Only the last tile of
+// a split can hold a key at or beyond len; there, and only there, such a score
+// is set to -inf before the maximum, whatever K's bits were (a select, no
+// arithmetic). Every tile a wave runs has a live key, so m is finite from a
+// wave's first tile on: alpha = exp2(-inf) = 0 there and never exp2(-inf - -inf).
+// A wave without a tile keeps m = -inf, l = 0, O = 0.
+//
+// Output. O^T = V^T P^T, 128 d x 16 queries as eight 16 x 16 accumulators (d 16
+// u ..), one MFMA of k = 32 keys each per tile. P, rounded to bf16, stays where
+// the scores left it: slot e of lane r + 16 g is key kappa = 16 (e >> 2) + 4 g +
+// (e & 3), not the 8 g + e the instruction counts by, and the A operand pairs
+// it: lane i + 16 g, slot e holds V[kappa][16 u + i]. Two ds_read_b64_tr_b16 per
+// fragment: block g of 16 lanes reads the 4 x 16 block of rows 16 x + 4 g .. + 3,
+// columns 16 u .. + 15, lane i pointing at row i >> 2, elements 4 (i & 3) .. + 3,
+// and receives column i of the four rows, slots 4 x .. 4 x + 3.
+//
+// Tail. The descriptors are sized to the head's live rows, len x 256 bytes, and
+// the whole row offset is in the lane's offset register, which is what the
+// range check looks at: nothing at or past len is fetched, and the tile past a
+// wave's last is sent to bit 31, outside any window (no load has a branch
+// around it). An unfetched V row must not meet p = 0 as stale bits (0 x NaN):
+// every wave writes zeros over the V half of its ring once, before its first
+// load. From then on a V row holds zeros, or a row of V that a load left there,
+// or zeros that a clipped load wrote: finite in every case, so p = 0 gives 0.
+// K's half may hold anything; its masked scores are replaced, not multiplied.
+//
+// Merge. After its loop a wave waits for vmcnt(0) (its last, clipped stage) and
+// writes O^T, m and the quad's sum of l over the start of its own ring, which
+// nobody else touches; one barrier, the only one behind the start stamp's;
+// then thread (w, l) merges for accumulators 2 w and 2 w + 1 the four parts
+// under the workgroup's maximum (attn_weight: a part or a whole split without
+// a key weighs 0 and leaves m = -inf, l = 0, O = 0) and stores the split's
+// unnormalised f32 O, 8 KiB in the order [u][lane][4] of the accumulators (d =
+// 16 u + 4 (lane >> 4) + i, query lane & 15), and (m, l), 16 floats each, at
+// workgroup g of the workspace, which is [pass][head][split].
+// tenant_attention_decode_combine_kernel, launched right behind on the same
+// stream, merges the splits.
+//
+// Barriers. stamp_start's, the merge's and stamp_end's: all outside the loop
+// and outside every branch, reached by every wave whatever its tile count.
+//
+// Bounds. head < heads, split < splits from blockIdx.x < passes x heads x
+// splits. Loads: descriptor of len x 256 bytes at the head's K or V, len <= seq,
+// inside the buffer; an offset is below (seq + 128) x 256 < 2^24 or has bit 31
+// set, and the hardware clips both beyond len. LDS handed to a load: wave x
+// ring + stage x 16 KiB + operand x 8 KiB + n x 1 KiB + 16 lane + 15, inside the
+// wave's ring, wave-uniform. Fragment reads: row < 32, position < 16 of a
+// tile. The merge's 8 KiB + 128 bytes fit the smallest ring, 16 KiB. Q: row
+// head x 16 + r. Workspace: 2048 floats and 32 floats at blockIdx.x, 64-bit.
+//
+// Stamps and clocks are the gemm kinds' (clocked_end).
+//
+// hipcc -O3 for gfx950 reports (-Rpass-analysis=kernel-resource-usage) 96
+// VGPRs, 32 AGPRs, 46 SGPRs, no scratch and no spills, 131072 bytes of LDS and
+// an occupancy of 1 wave per SIMD at depth 2; 96 VGPRs, no AGPRs, 58 SGPRs,
+// 65536 bytes and 2 waves per SIMD at depth 1. On the card the default window
+// streams 5.53-5.56 TB/s on the whole card (0.78 of a streamer's 7.09 in the
+// same run) and 4.17-4.26 on half of it (0.68-0.69 of 6.16) at depth 2, and
+// 5.32-5.39 and 4.57-4.67 (0.75 and 0.74-0.76) at depth 1: depth 2 is the
+// default for the whole card's sake, and half a card would rather have depth
+// 1's eight waves per CU (profiles/attention_decode_cotenancy_results.md).
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"  // m0 is clobbered on purpose
+__device__ inline void attn_dma(int4v rsrc, const int4v* lds, uint32_t lane_off) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
+               :
+               : "s"(static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsPtr)lds))),
+                 "v"(lane_off), "s"(rsrc)
+               : "memory", "m0");
+}
+
+__global__ void __launch_bounds__(kBlock, kAdDepth == 1 ? 2 : 1)
+tenant_attention_decode_kernel(const int4v* __restrict__ q, const int4v* __restrict__ k,
+                               const int4v* __restrict__ v, f32x4* __restrict__ ws_o,
+                               float* __restrict__ ws_ml, uint32_t heads, uint32_t seq,
+                               uint32_t splits, uint32_t span,
+                               unsigned long long* __restrict__ rec,
+                               unsigned long long* __restrict__ clk) {
+  __shared__ int4v ring[kWavesPerGroup][kAdDepth][2][kAdTileVecs];  // [wave][stage][K, V]
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = lane & 15u, g = lane >> 4;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+  const uint32_t split = blockIdx.x % splits, head = blockIdx.x / splits % heads;
+  const uint32_t len = attn_decode_len(head, seq);
+  const uint32_t key0 = 128 * span * split;
+  const uint32_t live = key0 < len ? min(128 * span, len - key0) : 0u;
+  const uint32_t tiles = (live + kAdKeys - 1) / kAdKeys;
+  const uint32_t count = tiles > wave ? (tiles - wave + 3) / 4 : 0u;  // this wave's tiles
+  const uint64_t head_vecs = static_cast<uint64_t>(seq) * kAttnRowVecs;
+  const auto window = [&](const int4v* first) {
+    const uint64_t base = reinterpret_cast<uint64_t>(first);
+    return int4v{static_cast<int>(static_cast<uint32_t>(base)),
+                 static_cast<int>(static_cast<uint32_t>(base >> 32) & 0xFFFFu),
+                 static_cast<int>(len * 256u), kBufferWord3};
+  };
+  const auto rk = window(k + head * head_vecs);
+  const auto rv = window(v + head * head_vecs);
+  // What this lane loads with instruction n of a stage: of row 4 n + g the
+  // chunk that belongs at position r; n & 3 decides the key.
+  uint32_t load_at[4];
+#pragma unroll
+  for (uint32_t n = 0; n < 4; ++n) load_at[n] = g * 256 + 16 * (r ^ attn_k_key(4 * n + g));
+  // What it reads: of a K tile rows 16 t + r at chunk (4 s + g) ^ key; of a V
+  // tile row 4 g + (r >> 2) (+ 16 x), chunk 2 u + ((r >> 1) & 1) under that
+  // row's key, bytes 8 (r & 1) .. + 7 of it.
+  const uint32_t read_k = r * kAttnRowVecs, read_key = attn_k_key(r);
+  const uint32_t v_row = 4 * g + (r >> 2);
+  const uint32_t read_v = v_row * 256 + 8 * (r & 1u);
+  const uint32_t v_key = ((r >> 1) & 1u) ^ attn_k_key(v_row);
+
+  // The 16 loads of this wave's tile `at` into stage `to`.
+  const auto issue = [&](const int4v (*to)[kAdTileVecs], uint32_t at)
+      __attribute__((always_inline)) {
+    const uint32_t outside = at < count ? 0u : kBufferOutside;
+    const uint32_t tile_off = (key0 + kAdKeys * (wave + 4 * at)) * 256;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    uint32_t off[kAdLoads];
+#pragma unroll
+    for (uint32_t n = 0; n < kAdLoads; ++n) off[n] = (load_at[n & 3] + tile_off + 1024 * n) | outside;
+#pragma unroll
+    for (int n = 0; n < kAdLoads; ++n) attn_dma(rk, to[0] + 64 * n, off[n]);
+#pragma unroll
+    for (int n = 0; n < kAdLoads; ++n) attn_dma(rv, to[1] + 64 * n, off[n]);
+  };
+
+  bf16x8 qf[4];
+  f32x4 out[8];
+  float m = -__builtin_inff(), l = 0.0f;
+  // One tile: scores, online softmax, output.
+  const auto step = [&](const int4v (*from)[kAdTileVecs], uint32_t at)
+      __attribute__((always_inline)) {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kAdLoads + 2 * kAdLoads * (kAdDepth - 1)) : "memory");
+    f32x4 s[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+#pragma unroll
+    for (uint32_t sub = 0; sub < 4; ++sub) {
+      const uint32_t c = (4 * sub + g) ^ read_key;
+#pragma unroll
+      for (uint32_t t = 0; t < 2; ++t) {
+        const bf16x8 kf = __builtin_bit_cast(bf16x8, from[0][read_k + 16 * kAttnRowVecs * t + c]);
+        s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[sub], s[t], 0, 0, 0);
+      }
+    }
+    const uint32_t first = kAdKeys * (wave + 4 * at);  // within the split
+    if (first + kAdKeys > live) {  // the split's last tile: keys at or beyond len
+#pragma unroll
+      for (uint32_t t = 0; t < 2; ++t)
+#pragma unroll
+        for (uint32_t reg = 0; reg < 4; ++reg)
+          if (first + 16 * t + 4 * g + reg >= live) s[t][reg] = -__builtin_inff();
+    }
+    float top = s[0][0];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) top = __builtin_fmaxf(top, s[t][reg]);
+    const float m_new = __builtin_fmaxf(m, attn_quad<true>(top));  // finite: a live key
+    const float alpha = __builtin_amdgcn_exp2f((m - m_new) * kAttnScale);
+    m = m_new;
+    bf16x8 p;  // slot 4 t + reg
+    float sum = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const float e = __builtin_amdgcn_exp2f((s[t][reg] - m) * kAttnScale);
+        sum += e;
+        p[4 * t + reg] = static_cast<__bf16>(e);
+      }
+    l = l * alpha + sum;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) out[u] *= alpha;
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kAdLoads * (kAdDepth - 1)) : "memory");
+    const char* tile_v = reinterpret_cast<const char*>(from[1]);
+#pragma unroll
+    for (uint32_t u = 0; u < 8; ++u) {
+      short4v half[2];
+#pragma unroll
+      for (uint32_t x = 0; x < 2; ++x)
+        half[x] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (__attribute__((address_space(3))) short4v*)(tile_v + read_v + 16 * ((2 * u) ^ v_key) +
+                                                         16 * x * 256));
+      const short8 vf = __builtin_shufflevector(half[0], half[1], 0, 1, 2, 3, 4, 5, 6, 7);
+      out[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vf), p, out[u],
+                                                       0, 0, 0);
+    }
+  };
+
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  const unsigned long long t0 = stamp_start();
+  const int4v* pq = q + (static_cast<uint64_t>(head) * kAdQueries + r) * kAttnRowVecs + g;
+#pragma unroll
+  for (int sub = 0; sub < 4; ++sub) qf[sub] = __builtin_bit_cast(bf16x8, pq[4 * sub]);
+#pragma unroll
+  for (int u = 0; u < 8; ++u) out[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  for (int stage = 0; stage < kAdDepth; ++stage)  // V's half of the ring, once
+#pragma unroll
+    for (int n = 0; n < kAdLoads; ++n) ring[wave][stage][1][64 * n + lane] = int4v{0, 0, 0, 0};
+  // Q is in its registers here, and the compiler knows it: it counts its own
+  // loads only, so a wait for Q that it placed at the first use, inside the
+  // loop, would be a wait for the stage just issued in every step.
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]));
+  for (uint32_t i = 0; i + 1 < kAdDepth; ++i) issue(ring[wave][i], i);
+  for (uint32_t i = 0; i < count; ++i) {
+    issue(ring[wave][(i + kAdDepth - 1) % kAdDepth], i + kAdDepth - 1);
+    step(ring[wave][i % kAdDepth], i);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clipped stage past the last
+
+  // The wave's part over the start of its ring: O^T as [u][lane] f32x4, then m
+  // and l per query.
+  l = attn_quad<false>(l);
+  f32x4* part = reinterpret_cast<f32x4*>(&ring[0][0][0][0]);
+  constexpr int kPartVecs = sizeof(ring[0]) / 16;  // one wave's ring
+#pragma unroll
+  for (int u = 0; u < 8; ++u) part[wave * kPartVecs + 64 * u + lane] = out[u];
+  if (g == 0) {
+    float* ml = reinterpret_cast<float*>(part + wave * kPartVecs + 512);
+    ml[r] = m;
+    ml[kAdQueries + r] = l;
+  }
+  __syncthreads();
+  float weight[kWavesPerGroup], top = -__builtin_inff(), sum = 0.0f;
+#pragma unroll
+  for (int j = 0; j < kWavesPerGroup; ++j)
+    top = __builtin_fmaxf(top, reinterpret_cast<const float*>(part + j * kPartVecs + 512)[r]);
+#pragma unroll
+  for (int j = 0; j < kWavesPerGroup; ++j) {
+    const float* ml = reinterpret_cast<const float*>(part + j * kPartVecs + 512);
+    weight[j] = attn_weight(ml[r], top);
+    sum += weight[j] * ml[kAdQueries + r];
+  }
+  const uint64_t group = blockIdx.x;
+#pragma unroll
+  for (uint32_t u = 2 * wave; u < 2 * wave + 2; ++u) {
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int j = 0; j < kWavesPerGroup; ++j) acc += weight[j] * part[j * kPartVecs + 64 * u + lane];
+    ws_o[group * (kAdSplitFloats / 4) + 64 * u + lane] = acc;
+  }
+  if (threadIdx.x < kAdQueries) {
+    ws_ml[group * (2 * kAdQueries) + r] = top;
+    ws_ml[group * (2 * kAdQueries) + kAdQueries + r] = sum;
+  }
+  clocked_end(rec, clk, c0, t0);
+}
+#pragma clang diagnostic pop
+
+// Merges the splits of a head: workgroup n of passes x heads reads the `splits`
+// parts of (pass, head) n from the workspace, thread (w, lane) the same
+// accumulators 2 w and 2 w + 1 at the same lane as in the main kernel's merge,
+// weighs them under the head's maximum (attn_weight; split 0 always has a key,
+// len >= seq - 127 >= 1, so the sum is positive), divides by the sum and stores
+// O as bf16, [pass][head][16][128]: query lane & 15, d = 16 u + 4 (lane >> 4) +
+// 0..3, one 8-byte store. It runs for one split too: one code path. Its stamps
+// go to the launch's record, which is a minimum and a maximum and so spans
+// both kernels; it adds nothing to the clock words. No barrier but the
+// stamps'. Every index is 64-bit and below passes x heads x splits x 2048 (or
+// x 32) of the workspace, and n x 2048 + 2047 of O.
+__global__ void __launch_bounds__(kBlock)
+tenant_attention_decode_combine_kernel(const f32x4* __restrict__ ws_o,
+                                       const float* __restrict__ ws_ml,
+                                       short4v* __restrict__ o, uint32_t splits,
+                                       unsigned long long* __restrict__ rec) {
+  const unsigned long long t0 = stamp_start();
+  const uint32_t lane = threadIdx.x & 63u, r = lane & 15u, g = lane >> 4;
+  const uint32_t wave = threadIdx.x / 64;
+  const uint64_t first = static_cast<uint64_t>(blockIdx.x) * splits;
+  float top = -__builtin_inff(), sum = 0.0f;
+  for (uint32_t s = 0; s < splits; ++s)
+    top = __builtin_fmaxf(top, ws_ml[(first + s) * (2 * kAdQueries) + r]);
+  f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+  for (uint32_t s = 0; s < splits; ++s) {
+    const float* ml = ws_ml + (first + s) * (2 * kAdQueries);
+    const float weight = attn_weight(ml[r], top);
+    sum += weight * ml[kAdQueries + r];
+#pragma unroll
+    for (uint32_t x = 0; x < 2; ++x)
+      acc[x] += weight * ws_o[(first + s) * (kAdSplitFloats / 4) + 64 * (2 * wave + x) + lane];
+  }
+  const float scale = 1.0f / sum;
+#pragma unroll
+  for (uint32_t x = 0; x < 2; ++x) {
+    short4v four;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      four[j] = __builtin_bit_cast(short, static_cast<__bf16>(acc[x][j] * scale));
+    o[(static_cast<uint64_t>(blockIdx.x) * kAdSplitFloats + r * kAttnDim + 16 * (2 * wave + x) +
+       4 * g) / 4] = four;
+  }
+  stamp_end(rec, t0);
+}
+
 // What the reference kernel adds up through LDS: the block's maximum, the
 // last operand winning when it is not a number so that one is never lost, or
 // its sum. Every thread gets the result.
@@ -2412,27 +2806,32 @@ __device__ inline double bf16_to_double(unsigned short bits) {
 // against it. Scores of keys 0 .. row (one key per thread at a time, into the
 // workgroup's own seq doubles of `scratch`), their maximum, exp and the sum,
 // then thread d < 128 the weighted sum over V's column d, divided by the sum.
+// With `decode` the head has q_rows = 16 rows of Q and of O and every row sees
+// keys 0 .. len(head) - 1 (attn_decode_len); otherwise q_rows = seq.
 // worst is the maximum over all workgroups of |O - reference|, kept as the
 // bits of a non-negative double, which order as the doubles do and put a
 // not-a-number above everything. Every index is below its buffer's size:
-// sample < passes x heads x seq by construction of the samples, key <= row <
-// seq.
+// sample < passes x heads x q_rows by construction of the samples, key <= last
+// < seq.
 __global__ void __launch_bounds__(kBlock)
 tenant_attention_reference_kernel(const unsigned short* __restrict__ q,
                                   const unsigned short* __restrict__ k,
                                   const unsigned short* __restrict__ v,
                                   const unsigned short* __restrict__ o,
                                   const uint32_t* __restrict__ samples, uint32_t heads,
-                                  uint32_t seq, double* __restrict__ scratch,
+                                  uint32_t q_rows, uint32_t seq, bool decode,
+                                  double* __restrict__ scratch,
                                   unsigned long long* __restrict__ worst) {
   __shared__ double red[kBlock];
   const uint32_t pass = samples[3 * blockIdx.x], head = samples[3 * blockIdx.x + 1];
   const uint32_t row = samples[3 * blockIdx.x + 2];
   const uint64_t head_at = static_cast<uint64_t>(head) * seq * kAttnDim;
-  const unsigned short* qr = q + head_at + static_cast<uint64_t>(row) * kAttnDim;
+  const uint64_t q_at = (static_cast<uint64_t>(head) * q_rows + row) * kAttnDim;
+  const uint32_t last = decode ? attn_decode_len(head, seq) - 1 : row;  // < seq
+  const unsigned short* qr = q + q_at;
   double* score = scratch + static_cast<uint64_t>(blockIdx.x) * seq;
   double top = -__builtin_inf();
-  for (uint32_t key = threadIdx.x; key <= row; key += kBlock) {
+  for (uint32_t key = threadIdx.x; key <= last; key += kBlock) {
     const unsigned short* kr = k + head_at + static_cast<uint64_t>(key) * kAttnDim;
     double dot = 0.0;
     for (int d = 0; d < kAttnDim; ++d) dot += bf16_to_double(qr[d]) * bf16_to_double(kr[d]);
@@ -2441,7 +2840,7 @@ tenant_attention_reference_kernel(const unsigned short* __restrict__ q,
   }
   top = attn_reduce<true>(red, top);
   double sum = 0.0;
-  for (uint32_t key = threadIdx.x; key <= row; key += kBlock) {
+  for (uint32_t key = threadIdx.x; key <= last; key += kBlock) {
     score[key] = exp(score[key] - top);
     sum += score[key];
   }
@@ -2449,11 +2848,11 @@ tenant_attention_reference_kernel(const unsigned short* __restrict__ q,
   double error = 0.0;
   if (threadIdx.x < kAttnDim) {
     double acc = 0.0;
-    for (uint32_t key = 0; key <= row; ++key)
+    for (uint32_t key = 0; key <= last; ++key)
       acc += score[key] * bf16_to_double(v[head_at + static_cast<uint64_t>(key) * kAttnDim +
                                            threadIdx.x]);
-    const uint64_t at = (static_cast<uint64_t>(pass) * heads * seq * kAttnDim) + head_at +
-                        static_cast<uint64_t>(row) * kAttnDim + threadIdx.x;
+    const uint64_t at = (static_cast<uint64_t>(pass) * heads * q_rows * kAttnDim) + q_at +
+                        threadIdx.x;
     error = fabs(bf16_to_double(o[at]) - acc / sum);
   }
   error = attn_reduce<true>(red, error);
@@ -2465,12 +2864,15 @@ tenant_attention_reference_kernel(const unsigned short* __restrict__ q,
 
 enum class Kind : int {
   kFma, kStream, kCache, kChase, kMfma, kGemm, kGemmMxfp8, kGemmMxfp4, kDecodeMxfp8,
-  kDecodeMxfp4, kAttention
+  kDecodeMxfp4, kAttention, kAttentionDecode
 };
-constexpr int kKinds = 11;
+constexpr int kKinds = 12;
 // What a kind shares with others: nothing (plain), form and operands (mfma),
-// the bf16 GEMM, a block-scaled GEMM, the decode shape of one, or attention.
-enum class Family : int { kPlain, kMfma, kGemm, kMxGemm, kDecode, kAttention };
+// the bf16 GEMM, a block-scaled GEMM, the decode shape of one, attention, or
+// the decode shape of that.
+enum class Family : int {
+  kPlain, kMfma, kGemm, kMxGemm, kDecode, kAttention, kAttentionDecode
+};
 // Per kind: the kind itself (the table is indexed by it), name, family, the
 // form a block-scaled kind implies (kBf16 otherwise), workgroups per CU
 // (chase: one, that is one wave per SIMD; the gemms and attention: none, their
@@ -2494,7 +2896,9 @@ constexpr KindInfo kKindTable[kKinds] = {
     {Kind::kGemmMxfp4, "gemm-mxfp4", Family::kMxGemm, kMxfp4, 0, true, true},
     {Kind::kDecodeMxfp8, "decode-mxfp8", Family::kDecode, kMxfp8, 0, true, true},
     {Kind::kDecodeMxfp4, "decode-mxfp4", Family::kDecode, kMxfp4, 0, true, true},
-    {Kind::kAttention, "attention", Family::kAttention, kBf16, 0, true, true}};
+    {Kind::kAttention, "attention", Family::kAttention, kBf16, 0, true, true},
+    {Kind::kAttentionDecode, "attention-decode", Family::kAttentionDecode, kBf16, 0, true,
+     true}};
 constexpr bool kind_table_in_order() {
   for (int i = 0; i < kKinds; ++i)
     if (static_cast<int>(kKindTable[i].kind) != i) return false;
@@ -2509,6 +2913,10 @@ constexpr bool is_mxgemm(Kind k) {
   return kind_info(k).family == Family::kMxGemm || kind_info(k).family == Family::kDecode;
 }
 constexpr bool is_gemm(Kind k) { return kind_info(k).family == Family::kGemm || is_mxgemm(k); }
+// Whether a kind is attention, in either shape: O, the reference, max_error.
+constexpr bool is_attention(Kind k) {
+  return k == Kind::kAttention || k == Kind::kAttentionDecode;
+}
 
 // What plan_tenant needs of a block-scaled form, from MxGemm<F>; by form.
 struct MxFormInfo {
@@ -2586,6 +2994,10 @@ struct TenantResult {
   // attention only: rows and heads, every pass's O, the reference kernel's
   // scores, the rows it recomputed and the largest |O - reference| it found
   uint64_t seq = 0, heads = 0, out_bytes = 0, scratch_bytes = 0;
+  // attention-decode only: query rows per head (0: seq of them), splits of a
+  // head, 128-key units per split, the splits' f32 parts
+  uint64_t queries = 0, work_bytes = 0;
+  int splits = 0, span = 0;
   int checked_rows = 0;
   double max_error = 0.0;
   // flops (fma, mfma, gemm, attention), bytes (stream, cache) or hops (chase)
@@ -2753,18 +3165,51 @@ TenantResult plan_tenant(Kind kind, int cus, int iters, uint64_t bytes, int pass
                                 r.iters * (r.iters + 2);
       break;
     }
+    case Kind::kAttentionDecode: {
+      // agent/cotenancy.py states the same rule on its own
+      // (attention_decode_shape). Per head 16 rows of Q, 4096 bytes, and a row
+      // of K plus one of V, 512 bytes, per key of capacity.
+      if (iters <= 0) iters = kAttnDefaultIters;
+      r.iters = std::min(iters, kAttnMaxIters);  // capacity in units of 128 keys
+      r.seq = static_cast<uint64_t>(128) * r.iters;
+      r.queries = kAdQueries;
+      const uint64_t heads = bytes == 0 ? kAdDefaultHeads : bytes / (512 * r.seq + 4096);
+      r.heads = std::min<uint64_t>(std::max<uint64_t>(heads, 1), kAttnMaxHeads);
+      r.bytes = (512 * r.seq + 4096) * r.heads;
+      // About 2048 workgroups a pass, a split no shorter than 1024 keys.
+      r.splits = std::min(std::max(kAdTargetGroups / static_cast<int>(r.heads), 1),
+                          (r.iters + 7) / 8);
+      r.span = (r.iters + r.splits - 1) / r.splits;
+      plan_gemm_grid(r, static_cast<int>(r.heads) * r.splits, passes, kAdDefaultPasses);
+      r.out_bytes = 2ULL * kAdSplitFloats * r.heads * r.passes;
+      r.work_bytes = static_cast<uint64_t>(r.workgroups) * (kAdSplitFloats + 2 * kAdQueries) * 4;
+      const uint64_t rows = r.queries * r.heads * r.passes;
+      r.checked_rows = static_cast<int>(std::min<uint64_t>(rows, kAttnSamples));
+      r.scratch_bytes = r.checked_rows * r.seq * sizeof(double);
+      uint64_t live = 0;  // the sum of the heads' lengths
+      for (uint32_t h = 0; h < r.heads; ++h)
+        live += attn_decode_len(h, static_cast<uint32_t>(r.seq));
+      // Two flops for Q K^T and two for P V per pair of a query and a live key.
+      r.work_per_launch = 4.0 * kAttnDim * kAdQueries * live * r.passes;
+      // The live rows of K and of V once, and Q once per split's workgroup.
+      r.load_bytes_per_launch = static_cast<uint64_t>(r.passes) *
+                                (512 * live + 4096 * r.heads * r.splits);
+      break;
+    }
   }
   return r;
 }
 
 // The rows the reference kernel recomputes, as (pass, head, row) triples: all
-// of them when there are no more than kAttnSamples; otherwise rows 0 and seq -
-// 1 of head 0 in the first and in the last pass, and the rest hashed from
+// of them when there are no more than kAttnSamples; otherwise the first and
+// the last row of head 0 in the first and in the last pass, and the rest hashed from
 // the seed and the sample's index.
 std::vector<uint32_t> attention_samples(const TenantResult& r, uint64_t seed) {
-  const uint32_t seq = static_cast<uint32_t>(r.seq), heads = static_cast<uint32_t>(r.heads);
+  // The rows of Q a head has: the decode shape's 16, else seq.
+  const uint32_t seq = static_cast<uint32_t>(r.queries ? r.queries : r.seq);
+  const uint32_t heads = static_cast<uint32_t>(r.heads);
   const uint32_t passes = static_cast<uint32_t>(r.passes);
-  const bool all = r.seq * r.heads * r.passes <= kAttnSamples;
+  const bool all = static_cast<uint64_t>(seq) * r.heads * r.passes <= kAttnSamples;
   const uint32_t key = mix32(static_cast<uint32_t>(seed) ^ kAttnKeySalt);
   std::vector<uint32_t> out;
   for (uint32_t i = 0; i < static_cast<uint32_t>(r.checked_rows); ++i) {
@@ -2786,7 +3231,9 @@ void attention_fill(hipStream_t stream, const TenantResult& r, int cus, void* bu
                     uint64_t seed) {
   hipLaunchKernelGGL(tenant_attention_fill_kernel, dim3(kGroupsPerCu * cus), dim3(kBlock), 0,
                      stream, static_cast<int4v*>(buf), r.bytes / 16,
-                     static_cast<uint32_t>(r.heads), static_cast<uint32_t>(r.seq),
+                     static_cast<uint32_t>(r.heads),
+                     static_cast<uint32_t>(r.queries ? r.queries : r.seq),
+                     static_cast<uint32_t>(r.seq),
                      mix32(static_cast<uint32_t>(seed) ^ kAttnKeySalt));
   HIP_CHECK(hipGetLastError());
 }
@@ -2798,6 +3245,28 @@ void attention_launch(hipStream_t stream, const TenantResult& r, const void* buf
   hipLaunchKernelGGL(tenant_attention_kernel, dim3(r.workgroups), dim3(kBlock), 0, stream, q,
                      q + operand, q + 2 * operand, static_cast<short4v*>(o),
                      static_cast<uint32_t>(r.heads), static_cast<uint32_t>(r.iters), rec, clk);
+  HIP_CHECK(hipGetLastError());
+}
+
+// One launch of an attention-decode tenant on `stream`: Q, K and V lie in `buf`
+// one behind the other, `work` takes the splits' f32 parts and their (m, l)
+// behind them, `o` every pass's O; the combine kernel follows the main one.
+void attention_decode_launch(hipStream_t stream, const TenantResult& r, const void* buf,
+                             void* work, void* o, unsigned long long* rec,
+                             unsigned long long* clk) {
+  const auto* q = static_cast<const int4v*>(buf);
+  const auto* k = q + r.heads * kAdQueries * kAttnRowVecs;
+  auto* ws_o = static_cast<f32x4*>(work);
+  auto* ws_ml = reinterpret_cast<float*>(ws_o + static_cast<uint64_t>(r.workgroups) *
+                                                    (kAdSplitFloats / 4));
+  hipLaunchKernelGGL(tenant_attention_decode_kernel, dim3(r.workgroups), dim3(kBlock), 0, stream,
+                     q, k, k + r.heads * r.seq * kAttnRowVecs, ws_o, ws_ml,
+                     static_cast<uint32_t>(r.heads), static_cast<uint32_t>(r.seq),
+                     static_cast<uint32_t>(r.splits), static_cast<uint32_t>(r.span), rec, clk);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(tenant_attention_decode_combine_kernel,
+                     dim3(static_cast<uint32_t>(r.heads) * r.passes), dim3(kBlock), 0, stream,
+                     ws_o, ws_ml, static_cast<short4v*>(o), static_cast<uint32_t>(r.splits), rec);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2820,13 +3289,14 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
   // {sum of shader cycles, sum of wall ticks} per launch, from zero.
   if (kind_info(r.kind).clocks) clks.h.assign(recs.h.size(), 0ULL);
   // attention: the rows to recompute, the reference's scores, its one word.
-  DevBuf samples, scratch;
+  DevBuf samples, scratch, work;
   std::vector<unsigned long long> worst_word;
   Mirror worst{worst_word};
   if (r.kind == Kind::kFma) {  // what a lane stores
     out.alloc(lanes * sizeof(float));
-  } else if (r.kind == Kind::kAttention) {  // every pass's O
+  } else if (is_attention(r.kind)) {  // every pass's O
     out.alloc(r.out_bytes);
+    if (r.work_bytes) work.alloc(r.work_bytes);
     const std::vector<uint32_t> rows = attention_samples(r, seed);
     samples.alloc(rows.size() * sizeof(uint32_t));
     HIP_CHECK(hipMemcpy(samples.p, rows.data(), rows.size() * sizeof(uint32_t),
@@ -2903,6 +3373,9 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
         case Kind::kAttention:
           attention_launch(g.s, r, buf.p, out.p, rec, clks.at(2 * slot));
           break;
+        case Kind::kAttentionDecode:
+          attention_decode_launch(g.s, r, buf.p, work.p, out.p, rec, clks.at(2 * slot));
+          break;
       }
     };
     switch (r.kind) {  // the fill
@@ -2933,6 +3406,7 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
         });
         break;
       case Kind::kAttention:
+      case Kind::kAttentionDecode:
         attention_fill(g.s, r, cus, buf.p, seed);
         break;
       case Kind::kFma:
@@ -2947,12 +3421,15 @@ void run_planned(TenantResult& r, int cus, const MaskWords& mask, int launches,
       launch(l);
       HIP_CHECK(hipEventRecord(ev[2 * l + 1].e, g.s));
     }
-    if (r.kind == Kind::kAttention) {  // the last launch's O against fp64, not timed
+    if (is_attention(r.kind)) {  // the last launch's O against fp64, not timed
       const auto* q = buf.as<const unsigned short>();
-      const uint64_t operand = r.bytes / 3 / 2;
-      go(dim3(r.checked_rows), tenant_attention_reference_kernel, q, q + operand,
-         q + 2 * operand, out.as<const unsigned short>(), samples.as<const uint32_t>(),
-         static_cast<uint32_t>(r.heads), static_cast<uint32_t>(r.seq), scratch.as<double>(),
+      const uint64_t q_rows = r.queries ? r.queries : r.seq;
+      const uint64_t operand = r.heads * r.seq * kAttnDim;
+      const auto* k = q + r.heads * q_rows * kAttnDim;
+      go(dim3(r.checked_rows), tenant_attention_reference_kernel, q, k, k + operand,
+         out.as<const unsigned short>(), samples.as<const uint32_t>(),
+         static_cast<uint32_t>(r.heads), static_cast<uint32_t>(q_rows),
+         static_cast<uint32_t>(r.seq), r.kind == Kind::kAttentionDecode, scratch.as<double>(),
          worst.at(0));
     }
     HIP_CHECK(hipStreamSynchronize(g.s));
@@ -3028,7 +3505,8 @@ TenantResult run_tenant(int device, const MaskWords& raw_mask, Kind kind, int la
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     r.free_bytes = free_b;
-    if (free_b < r.lead_bytes + r.bytes + r.scale_bytes + r.out_bytes + r.scratch_bytes + kGiB) {
+    if (free_b < r.lead_bytes + r.bytes + r.scale_bytes + r.out_bytes + r.scratch_bytes + r.work_bytes +
+                     kGiB) {
       r.skipped = true;
       return r;
     }
@@ -3173,6 +3651,19 @@ void register_cotenant(py::module_& m) {
             d["checked_rows"] = r.checked_rows;
             d["load_bytes_per_launch"] = r.load_bytes_per_launch;
             break;
+          case Family::kAttentionDecode:
+            d["seq"] = r.seq;
+            d["heads"] = r.heads;
+            d["head_dim"] = kAttnDim;
+            d["queries"] = r.queries;
+            d["splits"] = r.splits;
+            d["bytes"] = r.bytes;
+            d["out_bytes"] = r.out_bytes;
+            d["passes"] = r.passes;
+            d["max_error"] = r.max_error;
+            d["checked_rows"] = r.checked_rows;
+            d["load_bytes_per_launch"] = r.load_bytes_per_launch;
+            break;
         }
         if (clocks) last["clock_ghz"] = r.clock_ghz;
         d["work_per_launch"] = r.work_per_launch;
@@ -3205,7 +3696,8 @@ void register_cotenant(py::module_& m) {
       "cu_occupancy (None: a plain stream, which is what a process started "
       "under ROC_GLOBAL_CU_MASK uses); `kind` is \"fma\", \"stream\", "
       "\"cache\", \"chase\", \"mfma\", \"gemm\", \"gemm-mxfp8\", \"gemm-mxfp4\", "
-      "\"decode-mxfp8\", \"decode-mxfp4\" or \"attention\", anything else raises "
+      "\"decode-mxfp8\", \"decode-mxfp4\", \"attention\" or \"attention-decode\", anything "
+      "else raises "
       "ValueError before the device is touched. After one untimed "
       "launch, `launches` (1..64) launches of the same work run back to back "
       "on one stream, each between its own pair of events; the grid is 32 x "
@@ -3545,12 +4037,53 @@ void register_cotenant(py::module_& m) {
       "tile is issued but not counted), rates in GFLOP/s and the clocks. It "
       "takes no form, operands, loads or weights. attention_output returns "
       "every element of one pass's O.\n\n"
+      "attention-decode: a decode step's attention in bf16, the 16 query rows of "
+      "one step (a grouped-query group of 16, or 8 at two speculative positions) "
+      "against a head's K and V, which are read from memory once per pass: O = "
+      "softmax(Q K^T / sqrt(128)) V over the head's live keys, no causal mask, head "
+      "dimension 128. A head is one (sequence, KV head) pair. `iters` is the "
+      "capacity in units of 128 keys (default 64: seq = 8192; clamped to 1 .. "
+      "256); `bytes` is Q plus K plus V, heads = bytes // (512 seq + 4096) clamped "
+      "to 1 .. 1024 (0: 256 heads, 1 GiB of K and V), and the result reports the "
+      "bytes really used; the buffer is Q [head][16][128], then K [head][seq][128], "
+      "then V likewise, filled by attention's data rule. Head h is live for len(h) "
+      "= seq - 37 h % 128 keys; the keys beyond are in memory and must not count. "
+      "splits = 2048 // heads clamped to 1 .. ceil(iters / 8), span = ceil(iters / "
+      "splits) units, split s owning keys [128 span s, min(128 span (s + 1), len)); "
+      "`passes` is the whole steps of one launch, each into its own O (default "
+      "32; clamped to 1 .. 2^22 // (heads splits)). The grid is passes x heads x "
+      "splits workgroups. A split's tiles of 32 keys are dealt round to the four "
+      "waves, each with a ring of its own in LDS (2 stages of 8 KiB of K and 8 KiB "
+      "of V as built, 128 KiB per workgroup, one per CU; GPUPROBE_ATTN_DECODE_DEPTH=1: "
+      "1 stage, two per CU), filled by the 16-byte LDS-DMA load on descriptors of "
+      "the head's live rows and waited for with s_waitcnt vmcnt alone: no barrier "
+      "inside the key loop. Per tile a wave computes S^T = K Q^T in 8 "
+      "v_mfma_f32_16x16x32_bf16 with Q in registers, a column's maximum over four "
+      "lanes with v_permlane16_swap and v_permlane32_swap, the softmax online in "
+      "base 2 (a key at or beyond len scores -inf), and O^T += V^T P^T in 8 more "
+      "MFMAs with V read transposed by ds_read_b64_tr_b16. After one barrier the "
+      "waves' (m, l, O) are merged through LDS and stored, unnormalised f32, to a "
+      "workspace [pass][head][split]; a second kernel right behind on the same "
+      "stream merges the splits, divides by l and stores O as bf16, "
+      "[pass][head][16][128]. Both kernels stamp the launch's record; the clocks "
+      "are the first one's. Verified as attention is: checked_rows = min(256, "
+      "passes heads 16) rows of the last launch's O recomputed in fp64 over keys 0 "
+      ".. len - 1, max_error the largest difference. The result has seq, heads, "
+      "head_dim, queries = 16, splits, bytes, out_bytes = 4096 heads passes, "
+      "passes, max_error, checked_rows, load_bytes_per_launch = passes (512 x the "
+      "sum of the lengths + 4096 heads splits), the live K and V once and Q once "
+      "per workgroup, work_per_launch = passes 4 x 128 x 16 x the sum of the "
+      "lengths flops, rates in GFLOP/s and the clocks; the free-memory refusal "
+      "counts the workspace, 8320 bytes per workgroup, too. It takes no form, "
+      "operands, loads or weights. attention_output(kind=\"attention-decode\") "
+      "returns every element of one pass's O.\n\n"
       "Every launch records {earliest start, latest end} of wall_clock64() over "
       "all its workgroups; the clock runs at `tick_hz` "
       "(hipDeviceAttributeWallClockRate) for every process on the card. Returns "
       "{kind, [form,] applied_mask, tick_hz, workgroups, iters | [m, n, k,] bytes, "
       "[scale_bytes,] passes, (attention: seq, heads, head_dim, bytes, out_bytes, "
-      "passes, max_error, checked_rows, load_bytes_per_launch in place of these "
+      "passes, max_error, checked_rows, load_bytes_per_launch, attention-decode "
+      "the same with queries, splits after head_dim, in place of these "
       "and of what follows up to work_per_launch) "
       "checksum, [load_bytes_per_launch, [loads, stages, lds_bytes,] [weights,]] "
       "[operands, lds_bytes, lds_bytes_per_launch,] "
@@ -3566,11 +4099,16 @@ void register_cotenant(py::module_& m) {
 
   m.def(
       "attention_output",
-      [](int device, py::object mask, int iters, uint64_t bytes, uint64_t seed) {
+      [](int device, py::object mask, int iters, uint64_t bytes, uint64_t seed,
+         const std::string& kind) {
         const MaskWords raw = gpuprobe::mask_from_python(mask);
+        if (kind != "attention" && kind != "attention-decode")
+          throw py::value_error(
+              "attention_output: kind must be \"attention\" or \"attention-decode\"");
+        const bool decode = kind == "attention-decode";
         // The plan depends on no device; the fill's grid alone takes its CUs.
-        TenantResult r = plan_tenant(Kind::kAttention, 0, iters, bytes, 1, kBf16, false, false,
-                                     false);
+        TenantResult r = plan_tenant(decode ? Kind::kAttentionDecode : Kind::kAttention, 0, iters,
+                                     bytes, 1, kBf16, false, false, false);
         if (r.out_bytes > kAttnMaxOutput)
           throw py::value_error("attention_output: the output of " + std::to_string(r.heads) +
                                 " heads of " + std::to_string(r.seq) + " rows is " +
@@ -3581,17 +4119,21 @@ void register_cotenant(py::module_& m) {
           require_device(device);
           const int cus = gpuprobe::device_cus(device);
           const MaskWords words = raw.empty() ? MaskWords{} : gpuprobe::fit_mask(raw, cus);
-          DevBuf buf, out;
+          DevBuf buf, out, work;
           std::vector<unsigned long long> stamps{~0ULL, 0ULL, 0ULL, 0ULL};  // rec, clk
           Mirror marks{stamps};
           buf.alloc(r.bytes);
           out.alloc(r.out_bytes);
+          if (decode) work.alloc(r.work_bytes);
           marks.copy(true);
           HIP_CHECK(hipDeviceSynchronize());
           StreamGuard g;
           gpuprobe::open_stream(g, words, r.applied);
           attention_fill(g.s, r, cus, buf.p, seed);
-          attention_launch(g.s, r, buf.p, out.p, marks.at(0), marks.at(2));
+          if (decode)
+            attention_decode_launch(g.s, r, buf.p, work.p, out.p, marks.at(0), marks.at(2));
+          else
+            attention_launch(g.s, r, buf.p, out.p, marks.at(0), marks.at(2));
           HIP_CHECK(hipStreamSynchronize(g.s));
           HIP_CHECK(hipMemcpy(o.data(), out.p, r.out_bytes, hipMemcpyDeviceToHost));
         }
@@ -3599,13 +4141,20 @@ void register_cotenant(py::module_& m) {
         d["seq"] = r.seq;
         d["heads"] = r.heads;
         d["output"] = py::bytes(o);
+        if (decode) {
+          d["queries"] = r.queries;
+          d["splits"] = r.splits;
+        }
         return d;
       },
       py::arg("device") = 0, py::arg("mask") = py::none(), py::arg("iters") = 0,
-      py::arg("bytes") = 0, py::arg("seed") = 1,
+      py::arg("bytes") = 0, py::arg("seed") = 1, py::arg("kind") = "attention",
       "What one pass of an attention tenant computes: the fill and one launch of "
       "cu_tenant_run(kind=\"attention\")'s kernel for the same `iters`, `bytes` "
       "and `seed`, one pass. Returns {seq, heads, output}, output being O as "
       "little-endian bf16, [head][row][128], 256 * seq * heads bytes; raises "
-      "ValueError before the device is touched when that is more than 64 MiB.");
+      "ValueError before the device is touched when that is more than 64 MiB. "
+      "With kind \"attention-decode\" it is that kind's two kernels and the "
+      "result adds queries (16) and splits; output is [head][16][128], 4096 * "
+      "heads bytes. Any other kind raises ValueError.");
 }
